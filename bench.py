@@ -21,10 +21,21 @@ Timed region: inputs (parameters, code object) resident on the device, result le
 PyTorch provides the device buffer, the stream and torch.distributed only; every launch goes
 through the C ABI (libinflx_hip.so).
 
-After the timed region (N = 1 only, never part of `value`): `secondary` = BASELINE configs[2] (D5 4096^2 x 32
-parameter rows in one call) and configs[3] (EGNO 4096^2) timed with HIP events, `end_to_end` = the front-end call
-GeneralisedAL.complete_analysis(8192^2) -> six numpy arrays (PCIe-inclusive), `cpu_baseline` = the oracle on the
-host cores.
+A plain run does only what the headline figure needs: set-up, clock settling and warm-up, the K timed steps, the
+dump of --dump-outputs, the line.  Its `roofline` carries the figures that need no run of their own (bound, peak,
+stamped traffic, code object, HIP-event time of the timed region).
+
+--full adds, after the timed region (never part of `value`): the dominant kernel timed inside the steps and on its
+own (`roofline.achieved` / `frac` / `kernel_ms` ...), the per-rank figures, the summary sweep, and at N = 1
+`secondary` = BASELINE configs[2] (D5 4096^2 x 32 parameter rows in one call) and configs[3] (EGNO 4096^2) timed
+with HIP events, `end_to_end` = the front-end call GeneralisedAL.complete_analysis(8192^2) -> six numpy arrays
+(PCIe-inclusive), `cpu_baseline` = the oracle on the host cores (--no-extras / --no-cpu-baseline leave parts out).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the six quantities its last step left in the result block
+(a fixed, seeded sample of grid points when the block is larger than the cap): DIR/<name>.npy = the values as float64
+with NaN / +-Inf set to 0, DIR/<name>_nonfinite.npy = float32 codes 0 finite, 1 NaN, 2 +Inf, 3 -Inf.  Every file is
+finite; the pair gives back every value exactly (the model can yield NaN: the hyperbolic model's consistency condition is
+NaN at every point, in the reference's results as well).
 """
 
 from __future__ import annotations
@@ -46,6 +57,10 @@ BYTES_PER_POINT = 48  # 6 x f64 written, 0 read
 SETTLE_ROW_SWEEPS = 64
 PROFILE_ROUNDS = ("06", "05", "04", "03", "02", "01")  # profiles/rNN_traffic.json, rNN_valu.json, rNN_isa_mix.json: newest first
 SIMDS = 256 * 4
+# --dump-outputs: the six arrays of GeneralisedAL.complete_analysis, in the order of the result's last axis
+DUMP_NAMES = ("consistency", "epsilon_V", "epsilon_H", "eta_par", "delta", "omega")
+DUMP_MAX_POINTS = 1 << 19  # 6 x (8 + 4) B per point: 36 MiB, the whole dump stays under 64 MB
+DUMP_SEED = 20261016
 
 
 def host_threads() -> int:
@@ -461,6 +476,27 @@ def end_to_end(workloads, np, model: str, n: int, device: int):
     }
 
 
+def dump_outputs(path, out, torch, np):
+    """The six quantities of the result block `out` (rows, N0, N1, 6): whole (rows, N0, N1) arrays when the block holds at most
+    DUMP_MAX_POINTS grid points, else the values at one fixed, seeded sample of DUMP_MAX_POINTS flat point indices (sorted, the
+    same for every quantity and for every run with the same arguments).  path/<name>.npy: float64, non-finite values as 0;
+    path/<name>_nonfinite.npy: float32, 0 finite, 1 NaN, 2 +Inf, 3 -Inf."""
+    os.makedirs(path, exist_ok=True)
+    total = out.numel() // 6
+    flat = out.view(total, 6)
+    if total <= DUMP_MAX_POINTS:
+        vals = flat.cpu().numpy().reshape(out.shape)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=DUMP_MAX_POINTS, replace=False))  # every index < total
+        vals = flat.index_select(0, torch.from_numpy(idx).to(out.device)).cpu().numpy()
+    for k, name in enumerate(DUMP_NAMES):
+        v = np.ascontiguousarray(vals[..., k], dtype=np.float64)
+        fin = np.isfinite(v)
+        code = np.select([fin, np.isnan(v), v > 0], [0.0, 1.0, 2.0], 3.0).astype(np.float32)
+        np.save(os.path.join(path, f"{name}.npy"), np.where(fin, v, 0.0))
+        np.save(os.path.join(path, f"{name}_nonfinite.npy"), code)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -470,9 +506,15 @@ def main():
     ap.add_argument("--grid", dest="n", type=int, default=8192, help="grid points per axis")
     ap.add_argument("--rows-per-gpu", type=int, default=None, help="parameter rows per GPU and step (default: 1 at N = 1, 64 at N > 1 = BASELINE configs[4] on 8 GPUs)")
     ap.add_argument("--no-settle", dest="settle", action="store_false", help="skip the untimed clock-settling sweeps before the warm-up steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary workloads and the end-to-end call")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beside the headline figure (kernel roofline timings, "
+                    "per-rank figures, summary sweep; at N = 1 the secondary workloads, SURVEY 8(f) rows, end-to-end call and CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary workloads and the end-to-end call")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the six quantities of the last timed step as DIR/<name>.npy (float64, non-finite as 0) "
+                    "and DIR/<name>_nonfinite.npy (0 finite, 1 NaN, 2 +Inf, 3 -Inf); a seeded sample if large")
     opt = ap.parse_args()
+    if opt.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and opt.gpus > 1:
         raise SystemExit(self_launch(opt))
@@ -632,61 +674,66 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if opt.dump_outputs and rank == 0:  # what the last timed step left in the block, before anything below rewrites it
+        dump_outputs(opt.dump_outputs, out, torch, np)
+
     # dominant kernel, measured live with HIP events on the launch stream.  For a model whose values do
     # not depend on x[1] a sweep is two launches (per-row evaluation, ~4 % of the time, then the store
     # stream); the store stream is the dominant kernel and the one the roofline prices.
     row_path = lib.stage_info["out_mask"] & 2 == 0
-    # the dominant kernel on its own: the store stream of ONE parameter row of this rank's block (its launch is the
-    # same for every row; the timing-only mode needs the rows to fit one table batch)
-    one_row = args[:1]
-    ms_kernel_isolated = lib.sweep_device_timed(_native.OP_COMPLETE, one_row, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(5, opt.steps), dominant_only=row_path)
-    # ... and where the roofline prices it: INSIDE the step, exactly as the timed region enqueues it (all rows of the block, the
-    # per-row evaluation overlapping on the side stream, the cross-stream waits in place), from HIP event pairs recorded on the
-    # launch stream around every launch of the dominant kernel; per parameter row
-    ms_kernel = lib.sweep_device_timed(_native.OP_COMPLETE, args, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(2, min(opt.steps, 40 // rows_per_gpu)), in_pipeline=True) / rows_per_gpu
-    # ... and the whole step (all rows of the block, every launch of the call), per parameter row
-    ms_sweep = lib.sweep_device_timed(_native.OP_COMPLETE, args, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(2, min(opt.steps, 40 // rows_per_gpu))) / rows_per_gpu
-    # ... and ONE call from an idle handle (per-row evaluation + store stream between two events, the device drained before each call)
-    ms_single = lib.sweep_device_timed(_native.OP_COMPLETE, args, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(2, min(opt.steps, 40 // rows_per_gpu)), single_call=True) / rows_per_gpu
     points = N0 * N1
-    achieved = BYTES_PER_POINT * points / (ms_kernel * 1e-3) / 1e9
 
-    # every rank's own dominant-kernel time and roofline fraction, for the report of an N > 1 run
-    mine = torch.tensor([ms_kernel, ms_sweep, step_ms_events], dtype=torch.float64, device=comm_device)
-    if distributed:
-        gathered = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(gathered, mine)
-    else:
-        gathered = [mine]
-    per_rank = []
-    for r, g in enumerate(gathered):
-        k_ms, s_ms, e_ms = (float(v) for v in g.cpu())
-        gbps = BYTES_PER_POINT * points / (k_ms * 1e-3) / 1e9
-        per_rank.append({"rank": r, "kernel_ms": k_ms, "sweep_ms": s_ms, "step_ms_hip_events": e_ms, "achieved": gbps, "frac": gbps / HBM_PEAK_GBPS})
+    if opt.full:  # the figures that take runs of their own, all outside the timed region
+        # the dominant kernel on its own: the store stream of ONE parameter row of this rank's block (its launch is the
+        # same for every row; the timing-only mode needs the rows to fit one table batch)
+        one_row = args[:1]
+        ms_kernel_isolated = lib.sweep_device_timed(_native.OP_COMPLETE, one_row, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(5, opt.steps), dominant_only=row_path)
+        # ... and where the roofline prices it: INSIDE the step, exactly as the timed region enqueues it (all rows of the block, the
+        # per-row evaluation overlapping on the side stream, the cross-stream waits in place), from HIP event pairs recorded on the
+        # launch stream around every launch of the dominant kernel; per parameter row
+        ms_kernel = lib.sweep_device_timed(_native.OP_COMPLETE, args, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(2, min(opt.steps, 40 // rows_per_gpu)), in_pipeline=True) / rows_per_gpu
+        # ... and the whole step (all rows of the block, every launch of the call), per parameter row
+        ms_sweep = lib.sweep_device_timed(_native.OP_COMPLETE, args, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(2, min(opt.steps, 40 // rows_per_gpu))) / rows_per_gpu
+        # ... and ONE call from an idle handle (per-row evaluation + store stream between two events, the device drained before each call)
+        ms_single = lib.sweep_device_timed(_native.OP_COMPLETE, args, out.data_ptr(), nbytes, spec.extent, N0, N1, stream=stream, repeats=max(2, min(opt.steps, 40 // rows_per_gpu)), single_call=True) / rows_per_gpu
+        achieved = BYTES_PER_POINT * points / (ms_kernel * 1e-3) / 1e9
+
+        # every rank's own dominant-kernel time and roofline fraction, for the report of an N > 1 run
+        mine = torch.tensor([ms_kernel, ms_sweep, step_ms_events], dtype=torch.float64, device=comm_device)
+        if distributed:
+            gathered = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(gathered, mine)
+        else:
+            gathered = [mine]
+        per_rank = []
+        for r, g in enumerate(gathered):
+            k_ms, s_ms, e_ms = (float(v) for v in g.cpu())
+            gbps = BYTES_PER_POINT * points / (k_ms * 1e-3) / 1e9
+            per_rank.append({"rank": r, "kernel_ms": k_ms, "sweep_ms": s_ms, "step_ms_hip_events": e_ms, "achieved": gbps, "frac": gbps / HBM_PEAK_GBPS})
+
+        # outside the timed region: the statistics path of a sharded sweep -- every rank reduces its own block
+        # on the device (summary-only sweep), three six-element all-reduces combine the ranks (RCCL when N > 1)
+        stats_info = None
+        try:
+            t0 = time.perf_counter()
+            local = lib.sweep_stats(args, spec.extent, N0, N1)  # all rows of this rank's block
+            if distributed:
+                from inflatox_amd.distributed import all_reduce_summary
+
+                local = all_reduce_summary(local, device=comm_device)
+            stats_info = {
+                "ms": (time.perf_counter() - t0) * 1e3,
+                "nanmax": [None if not np.isfinite(v) else float(v) for v in local["max"]],
+                "non_nan": [int(v) for v in local["count"]],
+            }
+        except Exception as exc:  # noqa: BLE001 -- never let the optional extra break the benchmark line
+            stats_info = {"error": str(exc)[:200]}
 
     if distributed:
         device_names = [None] * world
         dist.all_gather_object(device_names, f"cuda:{local_rank} {device_name}")
     else:
         device_names = [f"cuda:{local_rank} {device_name}"]
-
-    # outside the timed region: the statistics path of a sharded sweep -- every rank reduces its own block
-    # on the device (summary-only sweep), three six-element all-reduces combine the ranks (RCCL when N > 1)
-    stats_info = None
-    try:
-        t0 = time.perf_counter()
-        local = lib.sweep_stats(args, spec.extent, N0, N1)  # all rows of this rank's block
-        if distributed:
-            from inflatox_amd.distributed import all_reduce_summary
-
-            local = all_reduce_summary(local, device=comm_device)
-        stats_info = {
-            "ms": (time.perf_counter() - t0) * 1e3,
-            "nanmax": [None if not np.isfinite(v) else float(v) for v in local["max"]],
-            "non_nan": [int(v) for v in local["count"]],
-        }
-    except Exception as exc:  # noqa: BLE001 -- never let the optional extra break the benchmark line
-        stats_info = {"error": str(exc)[:200]}
 
     if rank == 0:
         kernel = "inflx_sweep_rowstream6" if row_path else "inflx_sweep_tile_complete"
@@ -730,32 +777,35 @@ def main():
             "devices": device_names,
             "roofline": {
                 "bound": "hbm",
-                "achieved": achieved,
                 "peak": HBM_PEAK_GBPS,
                 "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS,
                 # HBM bytes per launch from the PMC passes on record for exactly this code object, else null
                 "traffic": traffic_rec["traffic_bytes"] if traffic_rec else None,
                 "traffic_source": traffic_src,
                 "code_object": cid,
                 "kernel": kernel,
+                "timed_region_ms_per_step_hip_events": step_ms_events,
+                "kernels_per_step": ["inflx_sweep_rowvals_complete", "inflx_sweep_rowstream6"] if row_path else ["inflx_sweep_tile_complete"],
+                "algorithmic_bytes_per_launch": BYTES_PER_POINT * points,
+            },
+        }
+        if opt.full:
+            line["roofline"].update({
+                "achieved": achieved,
+                "frac": achieved / HBM_PEAK_GBPS,
                 "kernel_ms": ms_kernel,
                 "kernel_timing": "HIP event pairs on the launch stream around every launch of the dominant kernel inside full steps (per parameter row); kernel_ms_isolated: the same kernel relaunched back to back on its own",
                 "kernel_ms_isolated": ms_kernel_isolated,
                 "sweep_ms": ms_sweep,  # whole step / parameter rows per step
                 "single_call_ms": ms_single,  # one call from an idle handle / parameter rows per call
                 "call_GBps": BYTES_PER_POINT * points / (ms_sweep * 1e-3) / 1e9,
-                "timed_region_ms_per_step_hip_events": step_ms_events,
-                "kernels_per_step": ["inflx_sweep_rowvals_complete", "inflx_sweep_rowstream6"] if row_path else ["inflx_sweep_tile_complete"],
-                "algorithmic_bytes_per_launch": BYTES_PER_POINT * points,
                 "per_rank": per_rank,
-            },
-        }
-        line["summary_sweep"] = stats_info
+            })
+            line["summary_sweep"] = stats_info
     if distributed:
         dist.barrier()
     if rank == 0:
-        if world == 1 and not opt.no_extras:
+        if opt.full and world == 1 and not opt.no_extras:
             del out
             torch.cuda.empty_cache()
             line["secondary"] = secondary_workloads(_native, workloads, torch, np, local_rank, stream)
@@ -775,7 +825,7 @@ def main():
                 line["end_to_end"] = end_to_end(workloads, np, opt.model, opt.n, local_rank)
             except Exception as exc:  # noqa: BLE001
                 line["end_to_end"] = {"error": str(exc)[:300]}
-        if world == 1 and not opt.no_cpu_baseline:
+        if opt.full and world == 1 and not opt.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(opt.model, spec.args, spec.extent)
             except Exception as exc:  # noqa: BLE001 -- the reported baseline must never cost the benchmark line

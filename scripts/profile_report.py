@@ -42,7 +42,7 @@ def main(d, rnd="02"):
     write, fetch = counter(os.path.join(d, "pmc_write"), "WRITE_SIZE"), counter(os.path.join(d, "pmc_fetch"), "FETCH_SIZE")
     traffic = {
         "_comment": "HBM traffic per launch of the bench kernels: rocprofv3 --pmc WRITE_SIZE and --pmc FETCH_SIZE in separate passes of "
-        "`python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline` (scripts/profile_bench.sh). Counter unit KB; bytes = KB*1024; FETCH_SIZE "
+        "`python3 bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-extras` (scripts/profile_bench.sh). Counter unit KB; bytes = KB*1024; FETCH_SIZE "
         "additionally doubled for gfx950 (MI355X_MICROARCH.md, HBM section).",
         "round": int(rnd),
         "workload": "hyperbolic 8192x8192 complete_analysis AoS",

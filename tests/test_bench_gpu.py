@@ -23,7 +23,7 @@ def _line(proc):
 
 def test_single_gpu_line():
     proc = subprocess.run(
-        [sys.executable, "bench.py", "--grid", "2048", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900
+        [sys.executable, "bench.py", "--grid", "2048", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900
     )
     line = _line(proc)
     for key in REQUIRED:
@@ -75,7 +75,7 @@ def test_two_rank_rehearsal(form):
     env = dict(os.environ, INFLX_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     rows = 3 if form == "plain" else None  # default at N > 1: 64 rows per GPU (BASELINE configs[4]); 2048^2 x 64 = 12.9 GB per rank
-    tail = ["bench.py", "--gpus", "2", "--grid", "2048", "--steps", "5", "--warmup", "2"] + (["--rows-per-gpu", str(rows)] if rows else [])
+    tail = ["bench.py", "--gpus", "2", "--grid", "2048", "--steps", "5", "--warmup", "2", "--full"] + (["--rows-per-gpu", str(rows)] if rows else [])
     rows = rows or 64
     if form == "plain":
         cmd = [sys.executable, *tail]
@@ -97,13 +97,25 @@ def test_two_rank_rehearsal(form):
     assert line["summary_sweep"]["non_nan"][1] == 2 * rows * 2048 * 2048
 
 
+def test_plain_two_rank_rehearsal():
+    """A plain N > 1 run (no --full): the timed steps of every rank, the MAX over ranks, and none of the --full figures."""
+    env = dict(os.environ, INFLX_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("WORLD_SIZE", None)
+    proc = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--grid", "1024", "--steps", "4", "--warmup", "1", "--rows-per-gpu", "2"],
+                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    line = _line(proc)
+    assert line["ranks"] == 2 and line["n_gpus"] == 2 and line["steps"] == 4 and line["comm_backend"] == "gloo"
+    assert abs(line["value"] - 2 * 2 * 1024 * 1024 * 4 / (line["ms_per_step"] * 4e-3)) / line["value"] < 1e-9
+    assert "summary_sweep" not in line and not {"kernel_ms", "per_rank"} & set(line["roofline"])
+
+
 def test_two_rank_rehearsal_sizes_the_block_to_the_free_hbm():
     """The first 8-GPU run must succeed unattended: the resident block is sized UP FRONT from the HBM that is free on the ranks'
     devices (bench.choose_rows_per_gpu), on every rank alike, and the line says which size ran.  Forced here with a 5 GB cap on the
     free figure (2048^2 x 6 x 8 B = 0.2 GB per row: 64 requested, 24 fit)."""
     env = dict(os.environ, INFLX_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", INFLX_BENCH_MAX_BLOCK_GB="5")
     env.pop("WORLD_SIZE", None)
-    proc = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--grid", "2048", "--steps", "3", "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    proc = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--grid", "2048", "--steps", "3", "--warmup", "1", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     line = _line(proc)
     cfg = line["config"]
     assert cfg["rows_per_gpu_requested"] == 64 and cfg["parameter_rows_per_gpu"] == 24 and cfg["parameter_rows_total"] == 48
@@ -121,7 +133,7 @@ def test_one_rank_through_rccl():
     env = dict(os.environ, INFLX_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    proc = subprocess.run([sys.executable, "bench.py", "--grid", "2048", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "2", "--no-extras", "--no-cpu-baseline"],
+    proc = subprocess.run([sys.executable, "bench.py", "--grid", "2048", "--steps", "3", "--warmup", "1", "--rows-per-gpu", "2", "--full", "--no-extras", "--no-cpu-baseline"],
                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     line = _line(proc)
     assert line["comm_backend"] == "nccl" and line["rccl_ranks"] == 1 and line["ranks"] == 1 and line["n_gpus"] == 1
@@ -129,3 +141,50 @@ def test_one_rank_through_rccl():
     assert len(line["devices"]) == 1 and line["devices"][0].startswith("cuda:0 ")
     assert line["summary_sweep"]["non_nan"][1] == 2 * 2048 * 2048
     assert abs(line["value"] - 2 * 2048 * 2048 * 3 / (line["ms_per_step"] * 3e-3)) / line["value"] < 1e-9
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps and carries none of the --full figures; --dump-outputs writes the six quantities of
+    the last timed step: whole arrays on a small grid (checked against the CPU oracle), a seeded sample on a larger one, the same
+    from run to run.  Every dumped file is finite: NaN / +-Inf travel as codes in <name>_nonfinite.npy."""
+    import numpy as np
+
+    import bench
+    import workloads
+    from conftest import compare, oracle_model
+
+    names = sorted(f"{name}{tail}.npy" for name in bench.DUMP_NAMES for tail in ("", "_nonfinite"))
+
+    def load(d, name):  # the values as the timed path left them: the finite part with the non-finite codes put back
+        val, code = np.load(d / f"{name}.npy"), np.load(d / f"{name}_nonfinite.npy")
+        assert val.dtype == np.float64 and code.dtype == np.float32 and val.shape == code.shape, name
+        assert np.isfinite(val).all() and np.isin(code, (0, 1, 2, 3)).all() and (val[code != 0] == 0).all(), name
+        return np.select([code == 1, code == 2, code == 3], [np.nan, np.inf, -np.inf], val)
+
+    def run(grid, steps, out_dir):
+        cmd = [sys.executable, "bench.py", "--grid", str(grid), "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out_dir)]
+        return _line(subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600))
+
+    line = run(512, 7, tmp_path / "small")
+    for key in REQUIRED:
+        assert key in line, key
+    assert line["steps"] == 7 and line["unit"] == "grid-points/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert abs(line["value"] - 512 * 512 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-9
+    assert not {"secondary", "next_rows", "end_to_end", "cpu_baseline", "summary_sweep"} & set(line)
+    assert not {"kernel_ms", "per_rank", "configs"} & set(line["roofline"])
+    spec, _ = workloads.artifact_for("hyperbolic")
+    want = oracle_model("hyperbolic")[0].complete_analysis(spec.args, spec.extent, 512, 512)
+    for k, name in enumerate(bench.DUMP_NAMES):
+        got = load(tmp_path / "small", name)
+        assert got.shape == (1, 512, 512), (name, got.shape)
+        compare(got[0], want[..., k], 1e-10, name)
+
+    dumps = []
+    for tag in ("a", "b"):
+        run(2048, 3, tmp_path / tag)
+        files = sorted(p.name for p in (tmp_path / tag).iterdir())
+        assert files == names and all(np.isfinite(np.load(tmp_path / tag / f)).all() for f in files)
+        assert sum((tmp_path / tag / f).stat().st_size for f in files) <= 64 * 2**20
+        dumps.append({name: load(tmp_path / tag, name) for name in bench.DUMP_NAMES})
+    for f, a in dumps[0].items():
+        assert a.shape == (bench.DUMP_MAX_POINTS,) and np.array_equal(a, dumps[1][f], equal_nan=True), f
