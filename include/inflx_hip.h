@@ -408,6 +408,43 @@ typedef enum inflx_gather {
 int inflx_sweep_allgather_multi_ex(inflx_multi* multi, int op, const double* p, size_t P, size_t n_p, void* const* d_full,
                                    size_t d_full_bytes, const double* start_stop, size_t N0, size_t N1, int gather);
 
+/*
+ * Background trajectories (the reference's inflatox.background.solve_eom, src/background_solver.rs): B trajectories of the model's
+ * equations of motion, one GPU lane each (csrc/inflx_background.h).  State (phi^0, phi^1, chi^0, chi^1, H, N); H starts from the
+ * Friedmann constraint H0 = sqrt((V + G_ab chi^a chi^b / 2) / 3), N and t from 0.
+ *   p          (P, n_p) parameter rows, P = 1 (shared) or B (one per trajectory)
+ *   init       (B, 4): phi^0, phi^1, chi^0, chi^1
+ *   rows       rows per trajectory: row 0 is the initial state, row k the state after k*substeps accepted steps
+ *   method     INFLX_EOM_RK4 (step doubling) or INFLX_EOM_RKF (Fehlberg 4(5))
+ *   max_err    error bound of the adaptive step (absolute Euclidean norm over phi, chi, H); dt > 0: fixed step, no error control
+ *   flags      INFLX_EOM_STOP_AT_END: a trajectory stops at the first accepted step with epsilon_H >= 1 (the row it stops in holds
+ *              that state); INFLX_EOM_FINAL_ONLY: no rows are kept -- `states` is (B, 6) and `t` (B,): where each trajectory stopped
+ *   states     (B, rows, 6) phi^0, phi^1, chi^0, chi^1, H, N;  t (B, rows);  efolds (B,): N at epsilon_H = 1 (linear in epsilon_H
+ *              across the step), NaN unless the trajectory ended;  status (B,) inflx_eom_status;  last_row (B,): the last row that
+ *              holds a state (the rows after it are NaN)
+ * Every output except `status` may be NULL.  The object `<artefact>.background` (CompilationArtifact.ensure_background()) is loaded on
+ * first use and must carry the artefact's MODEL_TAG; INFLX_ERR_SYMBOL when it does not exist, INFLX_ERR_VERSION when it belongs to
+ * another model.  Runs on the handle's stream; returns when the outputs are complete.
+ */
+typedef enum inflx_eom_method {
+  INFLX_EOM_RK4 = 0,
+  INFLX_EOM_RKF = 1
+} inflx_eom_method;
+typedef enum inflx_eom_flags {
+  INFLX_EOM_STOP_AT_END = 1,
+  INFLX_EOM_FINAL_ONLY = 2
+} inflx_eom_flags;
+typedef enum inflx_eom_status {
+  INFLX_EOM_COMPLETE = 0,   /* every requested step was taken */
+  INFLX_EOM_ENDED = 1,      /* epsilon_H reached 1 (INFLX_EOM_STOP_AT_END) */
+  INFLX_EOM_NONFINITE = 2,  /* the state or the equations of motion at it are not finite */
+  INFLX_EOM_REJECTED = 3,   /* 50 consecutive rejected steps */
+  INFLX_EOM_UNDERFLOW = 4   /* the step no longer moves t */
+} inflx_eom_status;
+int inflx_solve_eom(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps,
+                    int method, double max_err, double dt, unsigned flags, double* states, double* t, double* efolds, int8_t* status,
+                    int64_t* last_row);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """inflatox_amd -- MI355X-native grid-sweep path of inflatox.
 
 Public surface mirrors the reference package (python/inflatox/__init__.py:20-40):
-``InflationModelBuilder`` -> ``Compiler`` -> ``consistency_conditions.GeneralisedAL``.
+``InflationModelBuilder`` -> ``Compiler`` -> ``consistency_conditions.GeneralisedAL``, and ``background.solve_eom``.
 """
 
 from .compiler import CompilationArtifact, Compiler
@@ -14,6 +14,7 @@ __all__ = [
     "InflationModel",
     "InflationModelBuilder",
     "SymbolicCalculation",
+    "background",
     "consistency_conditions",
     "log_info",
     "log_warn",
@@ -36,9 +37,9 @@ def log_warn(msg: str) -> None:
 
 
 def __getattr__(name):
-    # consistency_conditions binds the native library on import; keep `import inflatox_amd` light
-    if name == "consistency_conditions":
+    # consistency_conditions and background bind the native library on import; keep `import inflatox_amd` light
+    if name in ("consistency_conditions", "background"):
         import importlib
 
-        return importlib.import_module(".consistency_conditions", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

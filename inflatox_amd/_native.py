@@ -31,6 +31,8 @@ OP_WIDTH = {OP_COMPLETE: 6, OP_CONSISTENCY: 1, OP_RAPIDTURN: 1, OP_EPSILON_V: 1,
 LAYOUT_AOS, LAYOUT_SOA = 0, 1
 SWEEP_DEFAULT, SWEEP_FORCE_TILE = 0, 1  # inflx_sweep_flags
 TIME_BACK_TO_BACK, TIME_DOMINANT_ONLY, TIME_IN_PIPELINE, TIME_SINGLE_CALL = range(4)  # inflx_timing
+EOM_RK4, EOM_RKF = 0, 1  # inflx_eom_method
+EOM_STOP_AT_END, EOM_FINAL_ONLY = 1, 2  # inflx_eom_flags
 GATHER_PEER_PUSH, GATHER_RCCL = 0, 1  # inflx_gather: the exchange step of inflx_sweep_allgather_multi_ex
 
 _DP = C.POINTER(C.c_double)
@@ -99,6 +101,10 @@ SIGNATURES = {
     "inflx_sweep_device_multi": (C.c_int, [C.c_void_p, C.c_int, _DP, _SIZE, _SIZE, C.POINTER(C.c_void_p), C.POINTER(_SIZE), _DP, _SIZE, _SIZE, C.c_int, C.POINTER(C.c_void_p)]),
     "inflx_sweep_allgather_multi": (C.c_int, [C.c_void_p, C.c_int, _DP, _SIZE, _SIZE, C.POINTER(C.c_void_p), _SIZE, _DP, _SIZE, _SIZE]),
     "inflx_sweep_allgather_multi_ex": (C.c_int, [C.c_void_p, C.c_int, _DP, _SIZE, _SIZE, C.POINTER(C.c_void_p), _SIZE, _DP, _SIZE, _SIZE, C.c_int]),
+    "inflx_solve_eom": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, C.POINTER(C.c_int8), C.POINTER(C.c_int64)],
+    ),
 }
 
 
@@ -113,7 +119,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -415,6 +421,31 @@ class InflatoxDevLib:
                 self._h, n.ctypes.data_as(C.POINTER(C.c_uint32)), n.size, _ptr(p), p.size, _ptr(ss), float(accuracy)
             )
         )
+
+    # ---- background trajectories (include/inflx_hip.h: inflx_solve_eom) -------------------------
+    def solve_eom(self, p, init, rows: int, substeps: int, method: int, max_err: float, dt: float, flags: int):
+        """B trajectories from ``init`` (B,4); ``p`` is (n_par,) or (B, n_par).  Returns (states, t, efolds, status, last_row):
+        states (B, rows, 6) and t (B, rows) -- (B, 6) and (B,) with ``EOM_FINAL_ONLY`` --, efolds, status (int8) and last_row (int64)
+        of shape (B,).  The background object must be in place (``CompilationArtifact.ensure_background``); arguments are checked
+        by the caller (inflatox_amd.background) and again by the library."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        B = init.shape[0]
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        final_only = bool(flags & EOM_FINAL_ONLY)
+        states = np.empty((B, 6) if final_only else (B, rows, 6))
+        t = np.empty((B,) if final_only else (B, rows))
+        efolds = np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        last_row = np.empty(B, dtype=np.int64)
+        _check(
+            self._lib.inflx_solve_eom(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(rows), int(substeps), int(method), float(max_err), float(dt), int(flags),
+                _ptr(states), _ptr(t), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)), last_row.ctypes.data_as(C.POINTER(C.c_int64)),
+            )
+        )  # fmt: skip
+        return states, t, efolds, status, last_row
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

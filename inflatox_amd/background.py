@@ -1,0 +1,190 @@
+"""Background trajectories: the model's equations of motion integrated on the GPU.
+
+``solve_eom`` is the reference's ``inflatox.background.solve_eom`` (python/inflatox/background.py) -- same signature, defaults and
+return value.  ``solve_eom_batch`` integrates many initial conditions or parameter rows at once, one GPU lane per trajectory, and
+``efolds_map`` places initial conditions on a sweep grid and returns the number of e-folds at the end of inflation there: the
+counterpart of a consistency map from ``GeneralisedAL.complete_analysis`` over the same grid.
+
+The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
+
+    dphi^a/dt = chi^a,   dchi^a/dt = -eom^a(phi, chi) - 3 H chi^a,   dH/dt = V - 3 H^2,   dN/dt = H
+
+with eom^a = Gamma^a_bc chi^b chi^c + G^ab d_b V the model's ``eom_fields``.  H starts from the Friedmann constraint
+H0 = sqrt((V + G_ab chi^a chi^b / 2) / 3); epsilon_H = (G_ab chi^a chi^b / 2) / H^2.  The steppers and the step-size control are
+described in csrc/inflx_background.h and DESIGN.md ("Background trajectories"); the kernels are csrc/inflx_background_kernels.hip,
+built into ``<artefact>.background`` on first use (``CompilationArtifact.ensure_background``).
+"""
+
+from __future__ import annotations
+
+import math
+import operator
+from typing import NamedTuple
+
+import numpy as np
+
+from . import _native
+from ._native import InflatoxShapeError
+from .compiler import CompilationArtifact
+
+__all__ = ["solve_eom", "solve_eom_batch", "efolds_map", "EoMSolution", "STATUS"]
+
+#: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
+COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW = 0, 1, 2, 3, 4
+STATUS = {
+    COMPLETE: "every requested step was taken",
+    ENDED: "epsilon_H reached 1 (stop_at_end)",
+    NONFINITE: "the state or the equations of motion at it are not finite",
+    REJECTED: "50 consecutive rejected steps",
+    UNDERFLOW: "the step size no longer moves t",
+}
+_METHODS = {"rk4": _native.EOM_RK4, "rkf": _native.EOM_RKF}
+
+
+class EoMSolution(NamedTuple):
+    """What :func:`solve_eom_batch` returns.  ``states`` (B, steps, 5): phi^0, phi^1, chi^0, chi^1, H (a strided view); ``t`` and
+    ``N`` (B, steps): cosmic time and e-folds of every row; ``status`` (B,) int8: ``STATUS`` codes; ``last_row`` (B,): the last row
+    that holds a state -- the rows after it are NaN; ``N_end`` (B,): N at epsilon_H = 1 with ``stop_at_end``, NaN otherwise."""
+
+    states: np.ndarray
+    t: np.ndarray
+    N: np.ndarray
+    status: np.ndarray
+    last_row: np.ndarray
+    N_end: np.ndarray
+
+
+def _dylib(artifact: CompilationArtifact) -> _native.InflatoxDevLib:
+    """The artefact's background object (built on first use) and one handle per artefact, opened on device 0 without the basis check."""
+    artifact.ensure_background()
+    lib = getattr(artifact, "_background_dylib", None)
+    if lib is None:
+        lib = _native.InflatoxDevLib(artifact.shared_object_path)
+        artifact._background_dylib = lib
+    return lib
+
+
+def _check_common(artifact, steps, max_err, solver, dt, substeps=1):
+    if getattr(artifact, "n_fields", None) != 2:
+        raise InflatoxShapeError(f"the background solver requires a 2-field model (model has {getattr(artifact, 'n_fields', None)} fields)")
+    try:
+        steps = operator.index(steps)
+        substeps = operator.index(substeps)
+    except TypeError:
+        raise ValueError("steps and substeps must be integers") from None
+    if steps < 1:
+        raise ValueError(f"steps must be at least 1 (got {steps})")
+    if substeps < 1 or substeps >= 2**32:
+        raise ValueError(f"substeps must be in [1, 2^32) (got {substeps})")
+    if (steps - 1) * substeps > 2**62:
+        raise ValueError("steps x substeps exceeds 2^62 accepted steps")
+    max_err = float(max_err)
+    if not (max_err > 0.0 and math.isfinite(max_err)):
+        raise ValueError(f"max_err must be a positive finite number (got {max_err})")
+    if solver not in _METHODS:
+        raise ValueError(f"unknown solver {solver!r}: choose 'rk4' or 'rkf'")
+    if dt is not None:
+        dt = float(dt)
+        if not (dt > 0.0 and math.isfinite(dt)):
+            raise ValueError(f"dt must be None (adaptive) or a positive finite step (got {dt})")
+    return steps, substeps, max_err, dt
+
+
+def _pars(artifact, pars, B):
+    p = np.ascontiguousarray(pars, dtype=np.float64)
+    n = artifact.n_parameters
+    if p.ndim <= 1:
+        if p.size != n:
+            raise InflatoxShapeError(f"model has {n} parameters (got {p.size})")
+        return p.reshape(n)
+    if p.ndim != 2 or p.shape != (B, n):
+        raise InflatoxShapeError(f"pars must have shape ({n},) or ({B}, {n}) (got {p.shape})")
+    return p
+
+
+def solve_eom_batch(artifact: CompilationArtifact, pars, steps: int, fields_init, derivatives_init, max_err: float = 1e-6, solver: str = "rkf", *,
+                    dt: float | None = None, substeps: int = 1, stop_at_end: bool = False) -> EoMSolution:  # fmt: skip
+    """B trajectories at once, one GPU lane each.  ``fields_init`` and ``derivatives_init`` are (B, 2); ``pars`` is (n_par,),
+    shared by every trajectory, or (B, n_par).  Row 0 of a trajectory is its initial state, row k the state after k*``substeps``
+    accepted steps.  ``solver``: ``"rkf"`` (Fehlberg 4(5)) or ``"rk4"`` (classical RK4, error from step doubling); ``max_err``: the
+    bound of the adaptive step on the absolute Euclidean norm of the error over phi, chi and H; ``dt``: a fixed step without error
+    control instead.  ``stop_at_end``: a trajectory stops at the first accepted step where epsilon_H >= 1 -- the row that step falls in
+    holds the state there, ``N_end`` the e-fold count at epsilon_H = 1, linear in epsilon_H across the step (see ``efolds_map`` for
+    its accuracy); a trajectory that starts with epsilon_H >= 1 ends at once, with ``N_end`` = 0 and row 0 its last row.  A trajectory
+    that stops for another reason (``status``) has NaN rows from there on.  However large ``substeps``, no kernel launch takes more
+    than 256 accepted steps per trajectory (a row may span launches).  Bad arguments raise before anything runs on the device."""
+    steps, substeps, max_err, dt = _check_common(artifact, steps, max_err, solver, dt, substeps)
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    B = x.shape[0]
+    p = _pars(artifact, pars, B)
+    init = np.concatenate([x, v], axis=1)
+    flags = _native.EOM_STOP_AT_END if stop_at_end else 0
+    states, t, n_end, status, last_row = _dylib(artifact).solve_eom(p, init, steps, substeps, _METHODS[solver], max_err, dt or 0.0, flags)
+    return EoMSolution(states[:, :, :5], t, states[:, :, 5], status, last_row, n_end)
+
+
+def solve_eom(artifact: CompilationArtifact, pars, steps: int, fields_init, derivatives_init, max_err: float = 1e-6, solver: str = "rk4", *,
+              dt: float | None = None) -> np.ndarray:  # fmt: skip
+    """The reference's ``solve_eom``: one trajectory as a C-contiguous (steps, 5) array with columns phi^0, phi^1, chi^0, chi^1, H;
+    row 0 is the initial state, row k the state after k accepted steps.  ``solver`` is ``"rk4"`` (the default, as in the reference)
+    or ``"rkf"``.  Extension (keyword-only): ``dt``, a fixed step.  Bit for bit ``solve_eom_batch`` with one trajectory; where that
+    trajectory stops early (``status``), the remaining rows are NaN."""
+    x = np.asarray(fields_init, dtype=np.float64).reshape(1, -1)
+    v = np.asarray(derivatives_init, dtype=np.float64).reshape(1, -1)
+    p = np.asarray(pars, dtype=np.float64)
+    if p.ndim != 1:
+        raise InflatoxShapeError(f"pars must be one parameter row (got shape {p.shape})")
+    sol = solve_eom_batch(artifact, p, steps, x, v, max_err, solver, dt=dt)
+    return np.ascontiguousarray(sol.states[0])
+
+
+def grid_points(start_stop, N0: int, N1: int):
+    """The field values of an (N0, N1) sweep grid, the sweeps' rule (inflx_coord): x = i * ((stop - start) / N) + start, the end point
+    excluded.  Returns (x0 (N0,), x1 (N1,))."""
+    ss = np.asarray(start_stop, dtype=np.float64).reshape(2, 2)
+    out = []
+    for (a, b), n in zip(ss, (N0, N1)):
+        spacing = (b - a) / float(n)
+        out.append(np.arange(n, dtype=np.float64) * spacing + a)
+    return out
+
+
+def efolds_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, derivatives_init=(0.0, 0.0), max_steps: int = 100_000,
+               max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """The number of e-folds at the end of inflation (epsilon_H = 1) from every point of an (N0, N1) grid over ``start_stop``
+    ((2, 2): [[x0_start, x0_stop], [x1_start, x1_stop]], the sweeps' layout and coordinate rule), all trajectories starting with the
+    velocities ``derivatives_init``.  NaN where inflation did not end within ``max_steps`` accepted steps or the trajectory stopped
+    for another reason; ``return_status=True`` returns ``(N_end, status)`` with the (N0, N1) int8 ``STATUS`` codes.  No rows are
+    stored (the kernels' final-only mode): memory is O(N0 * N1).
+
+    Accuracy: N_end is linear in epsilon_H across the accepted step in which epsilon_H reaches 1, and near the end of inflation the
+    adaptive steps span dN ~ 1e-2; that interpolation, not the integration, sets the error.  On the hyperbolic model at the default
+    ``max_err = 1e-8``, N_end is within 6e-4 e-folds of a DOP853 solution with an exact event (2e-5 .. 1e-4 at 1e-10); for more,
+    ``solve_eom_batch(..., stop_at_end=True)`` with a small fixed ``dt``.  A point already past the end of inflation (epsilon_H >= 1
+    at the start) has N_end = 0."""
+    _, _, max_err, _ = _check_common(artifact, max_steps, max_err, solver, None)
+    ss = np.asarray(start_stop, dtype=np.float64)
+    if ss.size != 4:
+        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
+    N0, N1 = operator.index(N0), operator.index(N1)
+    if N0 < 1 or N1 < 1:
+        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
+    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
+    if d.size != 2:
+        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
+    p = _pars(artifact, pars, 1)
+    if p.ndim != 1:
+        raise InflatoxShapeError("efolds_map takes one parameter row")
+    x0, x1 = grid_points(ss, N0, N1)
+    init = np.empty((N0 * N1, 4))
+    init[:, 0] = np.repeat(x0, N1)
+    init[:, 1] = np.tile(x1, N0)
+    init[:, 2:] = d
+    flags = _native.EOM_STOP_AT_END | _native.EOM_FINAL_ONLY
+    _, _, n_end, status, _ = _dylib(artifact).solve_eom(p, init, int(max_steps) + 1, 1, _METHODS[solver], max_err, 0.0, flags)
+    n_end = np.where(status == ENDED, n_end, np.nan).reshape(N0, N1)
+    status = status.reshape(N0, N1)
+    return (n_end, status) if return_status else n_end

@@ -37,7 +37,7 @@ import numpy as np
 import sympy
 from sympy.printing.c import C99CodePrinter
 
-from .staging import HIPInflatoxPrinter, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
+from .staging import HIPInflatoxPrinter, emit_eom_header, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
 from .symbolic import InflationModel
 from .version import __abi_version__, __version__
 
@@ -217,6 +217,8 @@ class CompilationArtifact:
         self.kernel_groups = ALL_GROUPS  # groups inside shared_object_path (Compiler.compile sets what it built)
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
+        self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
+        self._background_path = None
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -244,6 +246,51 @@ class CompilationArtifact:
             self._group_paths[group] = path
         return path
 
+    def eom_header_text(self) -> str:
+        """The generated header of the background equations of motion (``staging.emit_eom_header``), with this artefact's
+        parameter numbering and ``cse`` setting."""
+        if self._eom_recipe is None:
+            raise ValueError("this artefact does not know how it was compiled (not made by Compiler.compile)")
+        model, params, use_cse, max_cses = self._eom_recipe
+        cse = cse_vector = None
+        if use_cse:
+            # the reference's per-function sympy.cse calls, as Compiler makes them (a fresh symbol sequence per call)
+            def symbols():
+                for k in range(max_cses + 1):
+                    yield sympy.symbols(f"cse{k}")
+                raise Exception("Maximum number of common subexpressions reached!")
+
+            def cse(expr):
+                return sympy.cse(expr, symbols=symbols(), order="none", list=False)
+
+            def cse_vector(vector):
+                return sympy.cse(list(vector), symbols=symbols(), list=True)
+
+        return emit_eom_header(model, params, cse=cse, cse_vector=cse_vector)
+
+    def ensure_background(self) -> str:
+        """Extension: build the background code object of this model -- the trajectory kernels of
+        ``inflatox_amd.background`` (csrc/inflx_background_kernels.hip) -- and return its path, ``shared_object_path +
+        ".background"``, where ``libinflx_hip.so`` looks for it.  One hipcc step on first use from the core object's header and
+        options plus a header of the equations of motion (``staging.emit_eom_header``), cached like everything else; the object
+        carries the core object's ``MODEL_TAG``.  It lies outside the kernel groups (``KERNEL_GROUPS``, ``inflx_groups``)."""
+        path = self._background_path
+        if path is None or not os.path.exists(path):
+            if self._build is None or self._eom_recipe is None:
+                raise ValueError("this artefact does not know how it was compiled: its background object cannot be built (not made by Compiler.compile)")
+            header_text, options, tag = self._build
+            eom_text = self.eom_header_text()
+            cached, log, code = _build_background_object(header_text, eom_text, options, tag)
+            if code != 0:
+                print(log.decode("utf-8", "replace"))
+                raise Exception("hipcc compiler error while building the background object (see previous output)")
+            path = self.shared_object_path + ".background"
+            tmp = path + f".{os.getpid()}.tmp"
+            shutil.copyfile(cached, tmp)
+            os.replace(tmp, path)
+            self._background_path = path
+        return path
+
     def ensure_all_groups(self) -> list[str]:
         """Extension: every group beside the core object (what a C client of ``libinflx_hip.so`` wants in place before it starts)."""
         return [p for p in (self.ensure_group(g) for g in KERNEL_GROUPS) if p]
@@ -264,7 +311,9 @@ class CompilationArtifact:
 
     def __del__(self):
         if getattr(self, "auto_cleanup", False):
-            for path in [self.shared_object_path, *getattr(self, "_group_paths", {}).values()]:
+            for path in [self.shared_object_path, *getattr(self, "_group_paths", {}).values(), getattr(self, "_background_path", None)]:
+                if path is None:
+                    continue
                 try:
                     os.remove(path)
                 except OSError:
@@ -342,6 +391,41 @@ def _build_code_object(header_text: str, options: list[str], tag: str, groups: i
             os.replace(tmp_hdr, header_path)
         tmp_out = cached + f".{os.getpid()}.tmp"
         cmd = [hipcc_path(), *options, f"-DINFLX_KERNEL_GROUPS={groups}u", f'-DINFLX_MODEL_TAG="{tag}"', f"-I{_CSRC}", f'-DINFLX_MODEL_HEADER="{header_path}"', kernel_src, "-o", tmp_out]
+        proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        log, code = proc.stdout, proc.returncode
+        if code == 0:
+            os.replace(tmp_out, cached)
+    return cached, log, code
+
+
+_BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "inflx_background_abi.h")
+
+
+def _build_background_object(header_text: str, eom_text: str, options: list[str], tag: str):
+    """One hipcc step: the background kernels (csrc/inflx_background_kernels.hip) of the model whose core object has the content tag
+    ``tag`` (core header ``header_text``, hipcc ``options``) and whose equations of motion are ``eom_text``, into the content-addressed
+    cache as ``<tag>.bg<hash>.hsaco``; the hash covers the EoM header and the background sources (code only).  Returns (path, compiler
+    output, exit code)."""
+    cache = _cache_dir()
+    h = hashlib.sha256(eom_text.encode())
+    for f in _BACKGROUND_SOURCES:
+        with open(os.path.join(_CSRC, f), "r", encoding="utf-8") as fh:
+            h.update(_code_only(fh.read()).encode())
+    key = h.hexdigest()[:12]
+    header_path = os.path.join(cache, f"{tag}.h")
+    eom_path = os.path.join(cache, f"{tag}.eom{key}.h")
+    cached = os.path.join(cache, f"{tag}.bg{key}.hsaco")
+    log, code = b"", 0
+    if not os.path.exists(cached):
+        for path, text in ((header_path, header_text), (eom_path, eom_text)):
+            if not os.path.exists(path):
+                tmp = path + f".{os.getpid()}.tmp"
+                with open(tmp, "w") as fh:
+                    fh.write(text)
+                os.replace(tmp, path)
+        tmp_out = cached + f".{os.getpid()}.tmp"
+        cmd = [hipcc_path(), *options, f'-DINFLX_MODEL_TAG="{tag}"', f"-I{_CSRC}", f'-DINFLX_MODEL_HEADER="{header_path}"', f'-DINFLX_EOM_HEADER="{eom_path}"',
+               os.path.join(_CSRC, "inflx_background_kernels.hip"), "-o", tmp_out]  # fmt: skip
         proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
         log, code = proc.stdout, proc.returncode
         if code == 0:
@@ -627,6 +711,7 @@ class Compiler:
     # -- code generation ------------------------------------------------------------------------
     def _generate_hip_header(self) -> str:
         self.symbol_dict, params = self._number_parameters()
+        self._param_slots = params
         if not self.silent and self.cse:
             print("Converting sympy to HIP using common subexpression elimination...")
         cse = cse_vector = None
@@ -838,4 +923,5 @@ class Compiler:
         art._recipe = (self.symbolic_out, dict(self._init_kwargs))
         art.kernel_groups = self.kernel_groups
         art._build = (header, options, tag)
+        art._eom_recipe = (self.symbolic_out, dict(self._param_slots), self.cse, self.max_cses)
         return art

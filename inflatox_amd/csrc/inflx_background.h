@@ -1,0 +1,217 @@
+// Background trajectories: the integrator of a two-field model's equations of motion (inflatox_amd.background).
+//
+// State y = (phi^0, phi^1, chi^0, chi^1, H, N) in Planck units and cosmic time, the reference's system
+// (src/background_solver.rs EoM::f, EoM::g) with the e-fold count added:
+//     dphi^a/dt = chi^a
+//     dchi^a/dt = -eom^a(phi, chi) - 3 H chi^a      eom^a = Gamma^a_bc chi^b chi^c + G^ab d_b V   (the model's eom_fields)
+//     dH/dt     = V - 3 H^2
+//     dN/dt     = H
+// integrated as a plain first-order Runge-Kutta system (no Nystroem form):
+//     INFLX_BG_RKF  Fehlberg 4(5) with the reference's tableau; the state advances with the 4th-order weights, the error
+//                   is |5th - 4th|;
+//     INFLX_BG_RK4  classical RK4; the adaptive error comes from step doubling (one step of dt against two of dt/2, the
+//                   state advances with the two half steps).
+// Error norm: the absolute Euclidean norm over phi, chi and H (N is not part of it).  A step is accepted when
+// err <= 1.1 max_err; the next dt is dt * clamp(0.9 (max_err/err)^(1/5), 0.2, 5).  A fixed dt (> 0) takes every step without
+// error control.  Every loop is bounded: INFLX_BG_MAX_REJECTIONS consecutive rejections, or a dt that no longer moves t, stop
+// the lane with a status.
+//
+// Everything is INFLX_FN code over one lane's registers, so that tests/background_twin.cpp compiles the very same stepper for
+// the host.  The model enters through the generated inflx_eom_point (staging.emit_eom_header).
+#pragma once
+
+enum InflxBgStatus {
+  INFLX_BG_RUNNING = 0,    // (final value: every requested step was taken)
+  INFLX_BG_ENDED = 1,      // stop_at_end: epsilon_H reached 1
+  INFLX_BG_NONFINITE = 2,  // the state or the equations of motion at it are not finite
+  INFLX_BG_REJECTED = 3,   // INFLX_BG_MAX_REJECTIONS consecutive rejected steps
+  INFLX_BG_UNDERFLOW = 4,  // t + dt == t
+};
+
+enum InflxBgMethod { INFLX_BG_RK4 = 0, INFLX_BG_RKF = 1 };
+
+#define INFLX_BG_MAX_REJECTIONS 50
+#define INFLX_BG_FIRST_DT 1e-10
+
+// One lane: the state, the right-hand side at it (k1 of the next step, and the kinetic term G_ab chi^a chi^b), t and dt.
+struct InflxBgLane {
+  double y[6];
+  double f[6];
+  double kin;
+  double t;
+  double dt;
+};
+
+// dy/dt at y; kin = G_ab chi^a chi^b
+INFLX_FN void inflx_bg_rhs(const double* y, const double* __restrict__ p, double* f, double& kin) {
+  double o[4];
+  inflx_eom_point(y[0], y[1], y[2], y[3], p, o);
+  f[0] = y[2];
+  f[1] = y[3];
+  f[2] = -o[0] - 3.0 * y[4] * y[2];
+  f[3] = -o[1] - 3.0 * y[4] * y[3];
+  f[4] = o[2] - 3.0 * y[4] * y[4];
+  f[5] = y[4];
+  kin = o[3];
+}
+
+INFLX_FN bool inflx_bg_finite6(const double* v) {
+  bool ok = true;
+  for (int c = 0; c < 6; ++c) ok = ok && isfinite(v[c]);
+  return ok;
+}
+
+// the initial state: fields and velocities given, H from the Friedmann constraint H0 = sqrt((V + G_ab chi^a chi^b / 2) / 3), N = 0.
+// With stop_at_end, a state that is already past the end of inflation (epsilon_H >= 1) ends there: INFLX_BG_ENDED, N_end = 0.
+INFLX_FN int inflx_bg_init(InflxBgLane& s, const double* init, const double* __restrict__ p, double dt0, bool stop_at_end, double& n_end) {
+  double o[4];
+  inflx_eom_point(init[0], init[1], init[2], init[3], p, o);
+  s.y[0] = init[0];
+  s.y[1] = init[1];
+  s.y[2] = init[2];
+  s.y[3] = init[3];
+  s.y[4] = sqrt((o[2] + 0.5 * o[3]) / 3.0);
+  s.y[5] = 0.0;
+  s.t = 0.0;
+  s.dt = dt0;
+  inflx_bg_rhs(s.y, p, s.f, s.kin);
+  if (!(inflx_bg_finite6(s.y) && inflx_bg_finite6(s.f) && isfinite(s.kin))) return INFLX_BG_NONFINITE;
+  if (stop_at_end && 0.5 * s.kin / (s.y[4] * s.y[4]) >= 1.0) {
+    n_end = 0.0;
+    return INFLX_BG_ENDED;
+  }
+  return INFLX_BG_RUNNING;
+}
+
+// the right-hand side at the lane's state again (a launch resumes from a carried state)
+INFLX_FN void inflx_bg_resume(InflxBgLane& s, const double* __restrict__ p) { inflx_bg_rhs(s.y, p, s.f, s.kin); }
+
+// epsilon_H = (G_ab chi^a chi^b / 2) / H^2
+INFLX_FN double inflx_bg_epsilon(const InflxBgLane& s) { return 0.5 * s.kin / (s.y[4] * s.y[4]); }
+
+// one classical RK4 step of size h from (y, f0 = f(y))
+INFLX_FN void inflx_bg_rk4(const double* y, const double* f0, double h, const double* __restrict__ p, double* out) {
+  double k2[6], k3[6], k4[6], ys[6], kin;
+  for (int c = 0; c < 6; ++c) ys[c] = y[c] + h * (0.5 * f0[c]);
+  inflx_bg_rhs(ys, p, k2, kin);
+  for (int c = 0; c < 6; ++c) ys[c] = y[c] + h * (0.5 * k2[c]);
+  inflx_bg_rhs(ys, p, k3, kin);
+  for (int c = 0; c < 6; ++c) ys[c] = y[c] + h * (1.0 * k3[c]);
+  inflx_bg_rhs(ys, p, k4, kin);
+  for (int c = 0; c < 6; ++c) {
+    double acc = (1.0 / 6.0) * f0[c];
+    acc += (1.0 / 3.0) * k2[c];
+    acc += (1.0 / 3.0) * k3[c];
+    acc += (1.0 / 6.0) * k4[c];
+    out[c] = y[c] + h * acc;
+  }
+}
+
+// Fehlberg 4(5), the reference's tableau (src/background_solver.rs:232-240): out = 4th-order state, e = |5th - 4th| per component
+INFLX_FN void inflx_bg_rkf(const double* y, const double* f0, double h, const double* __restrict__ p, double* out, double* e) {
+  double k[6][6], ys[6], kin;
+  for (int c = 0; c < 6; ++c) k[0][c] = f0[c];
+  constexpr double A[6][5] = {
+      {0., 0., 0., 0., 0.},
+      {0.25, 0., 0., 0., 0.},
+      {3. / 32., 9. / 32., 0., 0., 0.},
+      {1932. / 2197., -7200. / 2197., 7296. / 2197., 0., 0.},
+      {439. / 216., -8., 3680. / 513., -845. / 4104., 0.},
+      {-8. / 27., 2., -3544. / 2565., 1859. / 4104., -11. / 40.},
+  };
+  constexpr double B5[6] = {16. / 135., 0., 6656. / 12825., 28561. / 56430., -9. / 50., 2. / 55.};
+  constexpr double B4[6] = {25. / 216., 0., 1408. / 2565., 2197. / 4104., -1. / 5., 0.};
+#pragma unroll
+  for (int s = 1; s < 6; ++s) {
+    for (int c = 0; c < 6; ++c) {
+      double acc = A[s][0] * k[0][c];
+#pragma unroll
+      for (int j = 1; j < s; ++j) acc += A[s][j] * k[j][c];
+      ys[c] = y[c] + h * acc;
+    }
+    inflx_bg_rhs(ys, p, k[s], kin);
+  }
+  for (int c = 0; c < 6; ++c) {
+    double a4 = B4[0] * k[0][c], a5 = B5[0] * k[0][c];
+#pragma unroll
+    for (int j = 1; j < 6; ++j) {
+      a4 += B4[j] * k[j][c];
+      a5 += B5[j] * k[j][c];
+    }
+    out[c] = y[c] + h * a4;
+    e[c] = fabs(h * a5 - h * a4);
+  }
+}
+
+INFLX_FN double inflx_bg_norm5(const double* e) {
+  double acc = e[0] * e[0];
+  for (int c = 1; c < 5; ++c) acc += e[c] * e[c];
+  return sqrt(acc);
+}
+
+// a trial step of size h: out = the state it reaches, return value = its error estimate (0 for a fixed step)
+template <int METHOD>
+INFLX_FN double inflx_bg_trial(const InflxBgLane& s, double h, bool adaptive, const double* __restrict__ p, double* out) {
+  if constexpr (METHOD == INFLX_BG_RKF) {
+    double e[6];
+    inflx_bg_rkf(s.y, s.f, h, p, out, e);
+    return adaptive ? inflx_bg_norm5(e) : 0.0;
+  } else {
+    if (!adaptive) {
+      inflx_bg_rk4(s.y, s.f, h, p, out);
+      return 0.0;
+    }
+    double big[6], half[6], fh[6], kin, e[6];
+    inflx_bg_rk4(s.y, s.f, h, p, big);
+    const double h2 = 0.5 * h;
+    inflx_bg_rk4(s.y, s.f, h2, p, half);
+    inflx_bg_rhs(half, p, fh, kin);
+    inflx_bg_rk4(half, fh, h2, p, out);
+    for (int c = 0; c < 6; ++c) e[c] = fabs(out[c] - big[c]);
+    return inflx_bg_norm5(e);
+  }
+}
+
+INFLX_FN double inflx_bg_factor(double max_err, double err) {
+  if (!(err > 0.0)) return 5.0;  // (err == 0: the largest growth)
+  const double q = 0.9 * pow(max_err / err, 0.2);
+  return q < 0.2 ? 0.2 : (q > 5.0 ? 5.0 : q);
+}
+
+// One accepted step (fixed_dt > 0: of that size, without error control).  Returns INFLX_BG_RUNNING, or the status that stops the
+// lane; `n_end` receives N at epsilon_H = 1 when stop_at_end ends it (linear in epsilon_H across the step).
+template <int METHOD>
+INFLX_FN int inflx_bg_step(InflxBgLane& s, const double* __restrict__ p, double max_err, double fixed_dt, bool stop_at_end, double& n_end) {
+  const bool adaptive = !(fixed_dt > 0.0);
+  const double eps0 = inflx_bg_epsilon(s), n0 = s.y[5];
+  double y1[6];
+  int rejections = 0;
+  for (;;) {
+    if (s.t + s.dt == s.t) return INFLX_BG_UNDERFLOW;
+    const double err = inflx_bg_trial<METHOD>(s, s.dt, adaptive, p, y1);
+    const bool finite = inflx_bg_finite6(y1) && isfinite(err);
+    if (!adaptive) {
+      if (!finite) return INFLX_BG_NONFINITE;
+      s.t += s.dt;
+      break;
+    }
+    if (finite && err <= 1.1 * max_err) {
+      s.t += s.dt;
+      s.dt *= inflx_bg_factor(max_err, err);
+      break;
+    }
+    s.dt *= finite ? inflx_bg_factor(max_err, err) : 0.2;
+    if (++rejections >= INFLX_BG_MAX_REJECTIONS) return INFLX_BG_REJECTED;
+  }
+  for (int c = 0; c < 6; ++c) s.y[c] = y1[c];
+  inflx_bg_rhs(s.y, p, s.f, s.kin);
+  if (!(inflx_bg_finite6(s.f) && isfinite(s.kin))) return INFLX_BG_NONFINITE;
+  if (stop_at_end) {
+    const double eps1 = inflx_bg_epsilon(s);
+    if (eps1 >= 1.0) {
+      n_end = n0 + (1.0 - eps0) / (eps1 - eps0) * (s.y[5] - n0);  // (eps0 < 1: a lane that starts at or past the end ends in init)
+      return INFLX_BG_ENDED;
+    }
+  }
+  return INFLX_BG_RUNNING;
+}

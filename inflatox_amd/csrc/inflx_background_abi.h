@@ -1,0 +1,49 @@
+// Layout shared by libinflx_hip.so (csrc/inflx_hip.cpp, inflx_solve_eom) and the background kernels
+// (csrc/inflx_background_kernels.hip): the kernels' argument block and the carry planes.  Both sides include this header; the
+// background object exports INFLX_BG_ABI, and the host refuses an object whose value differs from its own.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#define INFLX_BG_ABI_VERSION 2
+// the artefact ABI major a background object reports by default: the core object's (csrc/inflx_sweep_kernels.hip, overridable there
+// and here with -DINFLX_ABI_VERSION_MAJOR, which the background object is built with whenever the core object is)
+#define INFLX_BG_DEFAULT_ABI_MAJOR 5
+
+// carry planes [plane][lane] between launches
+enum InflxBgCarry {
+  INFLX_BG_CARRY_Y = 0,         // 0..5: phi^0, phi^1, chi^0, chi^1, H, N
+  INFLX_BG_CARRY_T = 6,
+  INFLX_BG_CARRY_DT = 7,
+  INFLX_BG_CARRY_NEND = 8,      // N at epsilon_H = 1 (NaN until the lane ends there)
+  INFLX_BG_CARRY_STATUS = 9,
+  INFLX_BG_CARRY_LAST_ROW = 10, // index of the last row that holds a state
+  INFLX_BG_CARRY_PENDING = 11,  // 1: the lane ended inside a row that has not been written yet (that row holds the end state)
+  INFLX_BG_CARRY_PLANES = 12,
+};
+
+// Argument block of inflx_bg_init and inflx_bg_advance_*.  A launch of the advance kernels processes the accepted-step indices
+// [step_begin, step_begin + steps) of every lane -- the same indices for all lanes, whether they still run or not --, and row r is
+// complete after step index r*substeps - 1; it goes to slot r - row_base of `rows`.
+struct InflxBgArgs {
+  const double* p;       // parameter rows of lane 0 of this launch
+  uint64_t p_stride;     // doubles between the parameter rows of two lanes (0: one row for all)
+  const double* init;    // (n, 4): phi^0, phi^1, chi^0, chi^1 (init kernel)
+  double* carry;         // [INFLX_BG_CARRY_PLANES][n]
+  double* rows;          // [slot][7][n]: y[0..5], t -- or NULL
+  uint64_t n;            // lanes
+  uint64_t step_begin;   // first accepted-step index of this launch
+  uint64_t row_base;     // row held by slot 0 of `rows`
+  uint32_t steps;        // accepted-step indices this launch processes (at most INFLX_BG_STEPS_PER_LAUNCH)
+  uint32_t substeps;     // accepted steps per row
+  uint32_t flags;        // bit 0: stop at epsilon_H = 1
+  uint32_t reserved;
+  double max_err;
+  double fixed_dt;       // > 0: fixed step
+};
+static_assert(sizeof(InflxBgArgs) == 96, "InflxBgArgs layout");
+static_assert(offsetof(InflxBgArgs, step_begin) == 48 && offsetof(InflxBgArgs, steps) == 64 && offsetof(InflxBgArgs, max_err) == 80,
+              "InflxBgArgs layout");
+
+// bound of one launch: accepted steps per lane (each of at most 50 trials)
+#define INFLX_BG_STEPS_PER_LAUNCH 256u

@@ -37,6 +37,7 @@
 #endif
 #include <unistd.h>
 
+#include "inflx_background_abi.h"
 #include "inflx_kernel_abi.h"
 
 namespace {
@@ -384,6 +385,10 @@ struct inflx_model {
   hipEvent_t chunk_done[2] = {nullptr, nullptr};
   hipEvent_t copy_done[2] = {nullptr, nullptr};
   hipEvent_t t0 = nullptr, t1 = nullptr;
+  // background trajectories (inflx_solve_eom): the object `<artefact>.background`, loaded on first use
+  hipModule_t bg_module = nullptr;
+  hipFunction_t bg_init = nullptr;
+  hipFunction_t bg_advance[2][2] = {};  // [method][store rows]
 };
 
 namespace {
@@ -1296,6 +1301,7 @@ void inflx_close(inflx_model* m) {
   if (m->side) (void)hipStreamDestroy(m->side);
   if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
   for (hipModule_t extra : m->attached) (void)hipModuleUnload(extra);
+  if (m->bg_module) (void)hipModuleUnload(m->bg_module);
   if (m->module) (void)hipModuleUnload(m->module);
   delete m;
 }
@@ -2815,6 +2821,186 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* mm, int op, const double* p, siz
         if (mm->push[k][j]) HIP_TRY(hipStreamSynchronize(mm->push[k][j]));
   }
   return INFLX_OK;
+}
+
+}  // extern "C"
+
+// ---- background trajectories (inflx_solve_eom) ------------------------------------------------------------------------------
+namespace {
+
+// the kernels' argument block and the carry planes: csrc/inflx_background_abi.h
+static_assert(kAbiMajor == INFLX_BG_DEFAULT_ABI_MAJOR, "a background object reports the core object's ABI major: change both together");
+// bounds of one call's passes: lanes per chunk, bytes of the device row buffer (the steps of one launch: INFLX_BG_STEPS_PER_LAUNCH)
+constexpr size_t kBgMaxLanes = size_t(1) << 20;
+constexpr size_t kBgRowBytes = size_t(256) << 20;
+
+// Load `<artefact>.background` beside the core object: it must carry the core object's MODEL_TAG.
+int need_background(inflx_model* m) {
+  if (m->bg_module) return INFLX_OK;
+  const std::string path = m->path + ".background";
+  FILE* fh = fopen(path.c_str(), "rb");
+  if (!fh)
+    return fail(INFLX_ERR_SYMBOL, "the background kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_background() "
+                "(inflatox_amd.background does on first use)", m->path.c_str(), path.c_str());
+  fclose(fh);
+  HIP_TRY(hipSetDevice(m->device));
+  hipModule_t module = nullptr;
+  hipError_t e = hipModuleLoad(&module, path.c_str());
+  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
+  auto bail = [&](int code) {
+    const std::string first = g_last_error;
+    (void)hipModuleUnload(module);
+    g_last_error = first;
+    return code;
+  };
+  uint16_t version[3] = {};
+  uint32_t abi = 0;
+  char tag[128] = {0};
+  int rc;
+  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_BG_ABI", &abi, sizeof abi, true)) ||
+      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
+    return bail(rc);
+  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_BG_ABI_VERSION || m->tag != tag)
+    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another ABI (tag \"%s\", expected \"%s\")",
+                     path.c_str(), m->path.c_str(), tag, m->tag.c_str()));
+  const char* names[2][2] = {{"inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows"}, {"inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows"}};
+  hipFunction_t init = nullptr, adv[2][2] = {};
+  if (hipModuleGetFunction(&init, module, "inflx_bg_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_bg_init", path.c_str()));
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b)
+      if (hipModuleGetFunction(&adv[a][b], module, names[a][b]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a][b]));
+  m->bg_module = module;
+  m->bg_init = init;
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) m->bg_advance[a][b] = adv[a][b];
+  note_sf_word(m, module);
+  return INFLX_OK;
+}
+
+// device buffers of one call, released on every way out
+struct BgBuffers {
+  double *p = nullptr, *init = nullptr, *carry = nullptr, *rows = nullptr;
+  ~BgBuffers() {
+    for (double* d : {p, init, carry, rows})
+      if (d) (void)hipFree(d);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps, int method,
+                    double max_err, double dt, unsigned flags, double* states, double* t, double* efolds, int8_t* status, int64_t* last_row) {
+  INFLX_SERIALISE(m);
+  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the background solver requires a 2-field model (model has %u fields)", m->dim);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
+  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
+  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
+  if (flags & ~(unsigned)(INFLX_EOM_STOP_AT_END | INFLX_EOM_FINAL_ONLY)) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
+  if (rows < 1) return fail(INFLX_ERR_ARG, "rows must be at least 1 (got %zu)", rows);
+  if (substeps < 1 || substeps > 0xffffffffu) return fail(INFLX_ERR_ARG, "substeps must be in [1, 2^32) (got %zu)", substeps);
+  if ((uint64_t)(rows - 1) > (UINT64_C(1) << 62) / substeps) return fail(INFLX_ERR_ARG, "rows x substeps exceeds 2^62 accepted steps");
+  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
+  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  int rc = need_background(m);
+  if (rc) return rc;
+  const bool final_only = (flags & INFLX_EOM_FINAL_ONLY) != 0;
+  const bool store = !final_only && (states || t);
+  hipStream_t s = m->stream;
+  const size_t nc_max = std::min(B, kBgMaxLanes);
+  size_t cap_rows = 0;  // rows the device row buffer holds
+  if (store) cap_rows = std::max<size_t>(2, std::min(rows, kBgRowBytes / (7 * sizeof(double) * nc_max)));
+  const uint64_t total_steps = (uint64_t)(rows - 1) * substeps;  // accepted-step indices of the call (checked against overflow above)
+  BgBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
+  if (store) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.rows), cap_rows * 7 * nc_max * sizeof(double)));
+  std::vector<double> host_rows(store ? cap_rows * 7 * nc_max : 0), host_carry(nc_max * INFLX_BG_CARRY_PLANES);
+  hipFunction_t advance = m->bg_advance[method == INFLX_EOM_RKF ? 1 : 0][store ? 1 : 0];
+
+  for (size_t c0 = 0; c0 < B; c0 += nc_max) {
+    const size_t n = std::min(nc_max, B - c0);
+    InflxBgArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = buf.init;
+    a.carry = buf.carry;
+    a.rows = store ? buf.rows : nullptr;
+    a.n = n;
+    a.substeps = (uint32_t)substeps;
+    a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    void* params[] = {&a};
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipModuleLaunchKernel(m->bg_init, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    // the device buffer holds rows [row_base, rows_done): rows_done = 1 + the rows completed by the steps taken so far
+    uint64_t row_base = 0, rows_done = 1, step = 0;
+    auto drain = [&]() -> int {
+      const size_t filled = (size_t)(rows_done - row_base);
+      if (!store || !filled) return INFLX_OK;
+      HIP_TRY(hipMemcpyAsync(host_rows.data(), buf.rows, filled * 7 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (size_t r = 0; r < filled; ++r) {
+        const double* plane = host_rows.data() + r * 7 * n;
+        const size_t row = (size_t)row_base + r;
+        if (states)
+          for (int c = 0; c < 6; ++c) {
+            const double* src = plane + (size_t)c * n;
+            double* dst = states + (c0 * rows + row) * 6 + c;
+            for (size_t l = 0; l < n; ++l) dst[l * rows * 6] = src[l];
+          }
+        if (t) {
+          const double* src = plane + 6 * n;
+          double* dst = t + c0 * rows + row;
+          for (size_t l = 0; l < n; ++l) dst[l * rows] = src[l];
+        }
+      }
+      row_base = rows_done;
+      return INFLX_OK;
+    };
+    while (step < total_steps) {
+      // at most INFLX_BG_STEPS_PER_LAUNCH steps, and no row beyond the last slot of the buffer: the row completed last must be
+      // < row_base + cap_rows, i.e. step + k <= (row_base + cap_rows) * substeps - 1 (>= step + substeps after every drain)
+      uint64_t k = std::min<uint64_t>(total_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
+      if (store) k = std::min<uint64_t>(k, (row_base + cap_rows) * substeps - 1 - step);
+      a.step_begin = step;
+      a.row_base = row_base;
+      a.steps = (uint32_t)k;
+      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+      step += k;
+      rows_done = 1 + step / substeps;
+      if (store && (rows_done - row_base == cap_rows || step == total_steps)) {
+        if ((rc = drain())) return rc;
+      }
+    }
+    if (store && (rc = drain())) return rc;  // (rows == 1: the initial state only)
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double* hc = host_carry.data();
+    for (size_t l = 0; l < n; ++l) {
+      status[c0 + l] = (int8_t)hc[INFLX_BG_CARRY_STATUS * n + l];
+      if (efolds) efolds[c0 + l] = hc[INFLX_BG_CARRY_NEND * n + l];
+      if (last_row) last_row[c0 + l] = (int64_t)hc[INFLX_BG_CARRY_LAST_ROW * n + l];
+      if (final_only) {
+        if (states)
+          for (int c = 0; c < 6; ++c) states[(c0 + l) * 6 + c] = hc[(size_t)(INFLX_BG_CARRY_Y + c) * n + l];
+        if (t) t[c0 + l] = hc[INFLX_BG_CARRY_T * n + l];
+      }
+    }
+  }
+  return sf_verdict(m);
 }
 
 }  // extern "C"

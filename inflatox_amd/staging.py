@@ -1031,3 +1031,57 @@ def _emit_basis_point(model, x0, x1, names, param_slots, tail, cse_vector):
         "double* __restrict__ o) {"
     )
     return head + "\n" + "\n".join(lines) + "\n}\n"
+
+
+def emit_eom_header(model, param_slots: dict, cse=None, cse_vector=None) -> str:
+    """The background equations of motion at one point, for the trajectory integrator (csrc/inflx_background.h):
+    ``inflx_eom_point(x0, x1, xd0, xd1, args, o)`` writes ``o[0..1]`` = eom^a = Gamma^a_bc xd^b xd^c + G^ab d_b V (the model's
+    ``eom_fields``, the reference's C functions ``eom_0`` / ``eom_1``), ``o[2]`` = V and ``o[3]`` = G_ab xd^a xd^b.
+
+    A header of its own, read only by the background code object (``CompilationArtifact.ensure_background``): the core header and
+    with it every sweep object and model tag stay as they are.  Like ``inflx_basis_point``: staged (identical nodes once, pow chains)
+    with every stage inline in one function, and the model's ``cse`` setting.  The velocities print as the plain names ``xd0`` /
+    ``xd1``; the stager classifies them as parameter-like (U), which only decides the order of the statements inside this one
+    function -- all of them are evaluated per call.  The metric's kinetic sum skips components that print as zero and adds the rest
+    left to right, as ``inflx_basis_point``'s inner products do."""
+    if model.dim != 2 or not model.eom_fields:
+        raise ValueError("the background equations need a two-field model with eom_fields")
+    x0, x1 = model.coordinates
+    xd = list(model.coordinate_tangents)
+    eoms = [sympy.sympify(e) for e in model.eom_fields]
+    potential = sympy.sympify(model.potential)
+    metric = [sympy.sympify(model.metric[i][j]) for i in range(2) for j in range(2)]
+    plain = C99CodePrinter()._print_Symbol
+    names = {x0: "x0", x1: "x1", xd[0]: "xd0", xd[1]: "xd1"}
+    for sym in set().union(*[e.free_symbols for e in eoms + metric + [potential]]) - set(names):
+        names[sym] = param_slots[plain(sym)]
+    functions = [cse_vector(eoms) if cse_vector is not None else ([], eoms)]
+    if cse is not None:
+        repl, red = cse(potential)
+        functions.append((repl, [red]))
+    else:
+        functions.append(([], [potential]))
+    functions.append(cse_vector(metric) if cse_vector is not None else ([], metric))
+    st = Stager(functions, x0, x1, names, staged=True)
+    lines = [ln for m in (U, R, C, P) for ln in st.lines[m]]
+    texts = list(st.outputs)
+    lines += [f"  o[0] = {texts[0]};", f"  o[1] = {texts[1]};", f"  o[2] = {texts[2]};"]
+    terms = []
+    for i in range(2):
+        for j in range(2):
+            t = texts[3 + 2 * i + j]
+            if t in ("0", "0.0"):
+                continue
+            lines.append(f"  const double g{i}{j} = {t};")
+            terms.append(f" + (g{i}{j} * xd{i} * xd{j})")
+    lines.append("  o[3] = 0.0" + "".join(terms) + ";")
+    return (
+        "// Generated by inflatox_amd.Compiler -- do not edit.\n"
+        f"// background equations of motion of model {model.model_name} (csrc/inflx_background.h); needs the model's core header first\n"
+        "#pragma once\n"
+        "// o[0], o[1]: eom^a = Gamma^a_bc xd^b xd^c + G^ab d_b V;  o[2]: V;  o[3]: G_ab xd^a xd^b\n"
+        "INFLX_FN void inflx_eom_point([[maybe_unused]] const double x0, [[maybe_unused]] const double x1, [[maybe_unused]] const double xd0, "
+        "[[maybe_unused]] const double xd1, [[maybe_unused]] const double* __restrict__ args, double* __restrict__ o) {\n"
+        + "\n".join(lines)
+        + "\n}\n"
+    )
