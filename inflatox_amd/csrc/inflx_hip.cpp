@@ -409,6 +409,10 @@ int read_global(inflx_model* m, const char* sym, T* dst, size_t bytes, bool exac
 // Put `count` doubles of parameters where kernels enqueued on `s` can read them; *d_params is the device
 // address.  A sweep re-launches with the same rows far more often than it changes them: when the current
 // slot already holds these values for this stream nothing is uploaded.
+// Ordering rule of the ring: a slot is released (release_params) on the stream of the LAST kernel that reads it -- params_reader(),
+// asked after evaluates_on_side_stream has decided where the sweep's tables go -- and is refilled only once that stream has passed
+// the release.  Released on any other stream, the slot looks free while its reader is still queued (behind other work on a
+// caller's stream), and four uploads later the reader evaluates another call's parameters.
 int acquire_params(inflx_model* m, const double* p, size_t count, hipStream_t s, const double** d_params) {
   inflx_model::ParamSlot& cur = m->pslot[m->pcur];
   if (cur.dev && cur.count == count && cur.stream == s && memcmp(cur.host, p, count * sizeof(double)) == 0) {
@@ -755,9 +759,12 @@ bool evaluates_on_side_stream(inflx_model* m, int op, int layout, size_t P, size
   return !m->tables_on_callers_stream;
 }
 // ... and on which stream does the LAST kernel that reads them run?  The tile kernels read the parameter rows too
-// (the point stage uses args[k]), after the table kernel; on the broadcast paths the store streams do not.
-bool last_reader_is_callers_stream(const inflx_model* m, int op, int layout, size_t P, size_t N1) {
-  return !(takes_row_stream(m, op, layout, P, N1) || takes_col_stream(m, op, layout, P, N1));
+// (the point stage uses args[k]), after the table kernel, and the fallback row kernel reads them itself: the caller's stream `s`.
+// On the broadcast paths the store streams do not: the last reader is the per-row / per-column evaluation, on the stream
+// evaluates_on_side_stream chose for it (the caller's for a lone sweep, the side stream otherwise).  Call it after that decision.
+hipStream_t params_reader(const inflx_model* m, int op, int layout, size_t P, size_t N1, hipStream_t s) {
+  if (takes_row_stream(m, op, layout, P, N1) || takes_col_stream(m, op, layout, P, N1)) return m->tables_on_callers_stream ? s : m->side;
+  return s;
 }
 
 // Has every kernel this handle enqueued earlier finished?  A sweep that arrives at an idle handle has nothing to overlap its
@@ -1362,7 +1369,10 @@ int inflx_sweep_plan_ex(const inflx_model* cm, int op, size_t P, size_t N1, size
     plan[2] = (uint32_t)((P + r.batch - 1) / r.batch);
     plan[3] = (uint32_t)r.replicas;
   } else if (takes_col_stream(m, op, layout, P, N1)) {
+    const size_t batch = col_stream_batch(op, layout, P, N1);
     plan[0] = INFLX_PATH_COL_STREAM;
+    plan[1] = (uint32_t)batch;
+    plan[2] = (uint32_t)((P + batch - 1) / batch);
   } else if ((m->info.out_mask & 2u) == 0 && op != INFLX_OP_QDIF && !(m->call_flags & INFLX_SWEEP_FORCE_TILE)) {
     plan[0] = INFLX_PATH_ROWS;
   } else {
@@ -1393,7 +1403,7 @@ int inflx_sweep_device_stats(inflx_model* m, const double* p, size_t P, size_t n
   // `eval`: the stream of the kernels that accumulate (the per-row / per-column evaluation of the broadcast paths on the
   // side stream, the tile kernels on the caller's)
   hipStream_t up = evaluates_on_side_stream(m, op, INFLX_AOS, P, N1, row_count) ? m->side : s;
-  hipStream_t eval = last_reader_is_callers_stream(m, op, INFLX_AOS, P, N1) ? s : m->side;
+  hipStream_t eval = params_reader(m, op, INFLX_AOS, P, N1, s);
   if (!m->d_stats) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_stats), 18 * sizeof(double)));
   inflx_summary init;
   for (int k = 0; k < 6; ++k) {
@@ -1466,7 +1476,7 @@ int inflx_sweep_device_ex(inflx_model* m, int op, const double* p, size_t P, siz
   const double* d_params = nullptr;
   if ((rc = acquire_params(m, p, P * n_p, up, &d_params))) return rc;
   rc = launch_grid(m, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s);
-  rc = release_params_after(m, last_reader_is_callers_stream(m, op, layout, P, N1) ? s : m->side, rc);
+  rc = release_params_after(m, params_reader(m, op, layout, P, N1, s), rc);
   if (rc == INFLX_OK && !m->sf_words.empty() && s != m->stream) {  // (see sf_done: the stream that finishes the sweep is the caller's)
     if (!m->sf_done) HIP_TRY(hipEventCreateWithFlags(&m->sf_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(m->sf_done, s));
@@ -1514,12 +1524,12 @@ int inflx_sweep_device_timed_ex(inflx_model* m, int op, const double* p, size_t 
     return INFLX_OK;
   }
   const int dominant_only = mode;
-  hipStream_t reader = last_reader_is_callers_stream(m, op, layout, P, N1) ? s : m->side;
   const double* d_params = m->pslot[m->pcur].dev;  // what the call above uploaded (or found in place)
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(m->side));
   // the repetitions are enqueued back to back: the shape of a sweep that arrives while its predecessor runs (tables on the side stream)
   (void)evaluates_on_side_stream(m, op, layout, P, N1, row_count, /*alone=*/false);
+  const hipStream_t reader = params_reader(m, op, layout, P, N1, s);
   // dominant_only == 2: the full sweeps, with an event pair around every dominant-kernel launch (at most 64 per sweep)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;
   struct Disarm {

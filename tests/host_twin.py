@@ -13,6 +13,22 @@ ROOT = os.path.dirname(HERE)
 _DP = C.POINTER(C.c_double)
 
 
+def sanitize_flags() -> list:
+    """INFLX_TEST_SANITIZE=1 (manual runs under LD_PRELOAD=libasan.so): the generated stage code and csrc/inflx_ops.h under ASan + UBSan."""
+    return ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("INFLX_TEST_SANITIZE") else []
+
+
+def build_command(cxx: str, contract: str, header_path: str, output_path: str) -> list:
+    """The compiler command that builds host_twin.cpp around the model header at ``header_path``."""
+    return [
+        cxx, "-O2", "-std=c++17", "-fPIC", "-shared", f"-ffp-contract={contract}",
+        *(["-mfma"] if contract != "off" else []),  # (a fused multiply-add needs the instruction)
+        "-fno-fast-math", "-Wno-unknown-pragmas", *sanitize_flags(),
+        f"-I{os.path.join(ROOT, 'inflatox_amd', 'csrc')}", f'-DINFLX_MODEL_HEADER="{header_path}"',
+        os.path.join(HERE, "host_twin.cpp"), "-o", output_path,
+    ]  # fmt: skip
+
+
 class HostTwin:
     def __init__(self, header_text: str, contract: str = "off", cxx: str = "g++"):
         """``cxx``: the host compiler; "clang++" (the ROCm image's) understands ``contract="on"`` -- fusion within a statement, the rule
@@ -21,9 +37,7 @@ class HostTwin:
             import shutil
 
             cxx = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-        # INFLX_TEST_SANITIZE=1 (manual runs under LD_PRELOAD=libasan.so): the generated stage code and csrc/inflx_ops.h under ASan + UBSan
-        sanitize = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g"] if os.environ.get("INFLX_TEST_SANITIZE") else []
-        tag = hashlib.sha1((header_text + contract + cxx + " ".join(sanitize)).encode()).hexdigest()[:16]
+        tag = hashlib.sha1((header_text + contract + cxx + " ".join(sanitize_flags())).encode()).hexdigest()[:16]
         d = os.path.join(tempfile.gettempdir(), "inflx_host_twin")
         os.makedirs(d, exist_ok=True)
         hdr = os.path.join(d, f"{tag}.h")
@@ -31,12 +45,7 @@ class HostTwin:
         if not os.path.exists(so):
             with open(hdr, "w") as fh:
                 fh.write(header_text)
-            cmd = [
-                cxx, "-O2", "-std=c++17", "-fPIC", "-shared", f"-ffp-contract={contract}", *(["-mfma"] if contract != "off" else []),  # (a fused multiply-add needs the instruction) "-fno-fast-math", "-Wno-unknown-pragmas", *sanitize,
-                f"-I{os.path.join(ROOT, 'inflatox_amd', 'csrc')}", f'-DINFLX_MODEL_HEADER="{hdr}"',
-                os.path.join(HERE, "host_twin.cpp"), "-o", so + ".tmp",
-            ]  # fmt: skip
-            subprocess.run(cmd, check=True)
+            subprocess.run(build_command(cxx, contract, hdr, so + ".tmp"), check=True)
             os.replace(so + ".tmp", so)
         self.lib = C.CDLL(so)
         self.lib.twin_grid.argtypes = [C.c_int, _DP, _DP, C.c_size_t, C.c_size_t, _DP]

@@ -222,3 +222,18 @@ def test_v01_of_its_own_on_the_gpu_matches_the_oracle(gpu_lib):
     assert not np.array_equal(H[0, 1], H[1, 0])
     x = pts[n1 + 7]
     compare(al.calc_H(x, args), om.hesse(x, args), 1e-12, "calc_H")
+
+
+def test_host_twin_command_keeps_sanitizer_and_ieee_flags(monkeypatch):
+    """INFLX_TEST_SANITIZE=1 builds the host twin under ASan + UBSan, and every build keeps -fno-fast-math (no compilation here)."""
+    import host_twin
+
+    monkeypatch.setenv("INFLX_TEST_SANITIZE", "1")
+    cmd = host_twin.build_command("g++", "on", "/x/model.h", "/x/twin.so")
+    for flag in ("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-fast-math", "-Wno-unknown-pragmas", "-mfma", "-ffp-contract=on"):
+        assert flag in cmd, (flag, cmd)
+    assert cmd[-2:] == ["-o", "/x/twin.so"] and '-DINFLX_MODEL_HEADER="/x/model.h"' in cmd
+    monkeypatch.delenv("INFLX_TEST_SANITIZE")
+    cmd = host_twin.build_command("g++", "off", "/x/model.h", "/x/twin.so")
+    assert "-fno-fast-math" in cmd and "-Wno-unknown-pragmas" in cmd and "-mfma" not in cmd
+    assert not any(f.startswith("-fsanitize") for f in cmd), cmd
