@@ -283,6 +283,51 @@ void prefault_range(char* begin, size_t bytes) {
   }
   for (auto& th : pool) th.join();
 }
+
+// A double-buffered device table: one kernel writes buffer b (on the side stream, or on the caller's for a sweep enqueued alone)
+// while the kernel that reads the other buffer still runs on the caller's stream; two events per buffer order its reuse.  The
+// row / column table of the broadcast paths and the stage tables of the tile path are one ring each.
+struct TableRing {
+  double* buf[2] = {nullptr, nullptr};
+  size_t cap[2] = {0, 0};                    // doubles
+  hipEvent_t ready[2] = {nullptr, nullptr};  // the kernel that writes buffer b finished
+  hipEvent_t free[2] = {nullptr, nullptr};   // the kernel that last read buffer b finished
+  bool used[2] = {false, false};
+  unsigned turn = 0;
+
+  bool create() {
+    // ordering-only events between two streams of this device: no system-scope fence needed (the kernels' own agent-scope
+    // release/acquire at their boundaries publishes the table)
+    for (int b = 0; b < 2; ++b)
+      if (hipEventCreateWithFlags(&ready[b], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
+          hipEventCreateWithFlags(&free[b], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess)
+        return false;
+    return true;
+  }
+  void destroy() {
+    for (int b = 0; b < 2; ++b) {
+      if (ready[b]) (void)hipEventDestroy(ready[b]);
+      if (free[b]) (void)hipEventDestroy(free[b]);
+      if (buf[b]) (void)hipFree(buf[b]);
+    }
+  }
+  // has every kernel that read one of the buffers finished?
+  bool idle() const {
+    for (int b = 0; b < 2; ++b)
+      if (used[b] && hipEventQuery(free[b]) != hipSuccess) return false;
+    return true;
+  }
+  // Replace buffer b by one of `doubles`.  The caller has waited for whatever may still use the old one -- what that is differs
+  // between the two rings (launch_broadcast, launch_tiles).
+  int grow(int b, size_t doubles) {
+    if (buf[b]) HIP_TRY(hipFree(buf[b]));
+    buf[b] = nullptr;
+    cap[b] = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf[b]), doubles * sizeof(double)));
+    cap[b] = doubles;
+    return INFLX_OK;
+  }
+};
 }  // namespace
 
 #define INFLX_SERIALISE(m) \
@@ -314,30 +359,14 @@ struct inflx_model {
   // on the side stream, double-buffered like the row table: the tables of launch n+1 are evaluated while the tile
   // kernel of launch n runs (the table kernel is a latency-bound chain on a few dozen workgroups)
   hipFunction_t stage_tables = nullptr;
-  double* d_stage_tab[2] = {nullptr, nullptr};
-  size_t d_stage_tab_cap[2] = {0, 0};  // doubles
-  hipEvent_t stage_ready[2] = {nullptr, nullptr};  // inflx_stage_tables finished writing buffer b
-  hipEvent_t stage_free[2] = {nullptr, nullptr};   // the tile kernel that last read buffer b finished
-  bool stage_used[2] = {false, false};
-  unsigned stage_turn = 0;
-  // decided per call by evaluates_on_side_stream, read by launch_tiles: a tile sweep that is ONE launch builds its tables on
-  // the caller's stream, in front of the tile kernel (no second stream, no event between the two)
-  bool tables_on_callers_stream = false;
-  // inflx_sweep_flags of the call that holds the lock (INFLX_SWEEP_FORCE_TILE: every grid point through the tile kernels even where
-  // the model ignores a grid axis); set and cleared by the *_ex entry points
-  unsigned call_flags = 0;
+  TableRing stage_ring;
   hipFunction_t tile_stats = nullptr, tile_stats_nostore = nullptr, rowvals_stats = nullptr;
   double* d_stats = nullptr;  // 18 x 8 bytes: min[6], max[6], count[6]
-  // Row-broadcast path: per-row results [P][rows][replicas][8], double-buffered.  The per-row
-  // evaluation of sweep n runs on `side` and overlaps the store stream of sweep n-1 on the caller's
-  // stream (it needs ~25 us of latency but hardly any bandwidth); events order table reuse.
-  double* d_row_table[2] = {nullptr, nullptr};
-  size_t d_row_table_cap[2] = {0, 0};
+  // Row-broadcast path: per-row results [P][rows][replicas][8], double-buffered (the column-broadcast path keeps its row images
+  // in the same ring).  The per-row evaluation of sweep n runs on `side` and overlaps the store stream of sweep n-1 on the
+  // caller's stream (it needs ~25 us of latency but hardly any bandwidth); events order table reuse.
+  TableRing row_ring;
   hipStream_t side = nullptr;
-  hipEvent_t table_ready[2] = {nullptr, nullptr};  // rowvals finished writing buffer b
-  hipEvent_t table_free[2] = {nullptr, nullptr};   // the store stream that last read buffer b finished
-  bool table_used[2] = {false, false};
-  unsigned table_turn = 0;
   // inflx_sweep_device_timed(..., dominant_only = 2): event pairs recorded around every dominant-kernel launch of the sweeps it
   // enqueues -- the kernel's duration inside the full pipeline (side-stream evaluation overlapping, cross-stream waits in place)
   std::vector<std::pair<hipEvent_t, hipEvent_t>>* probe = nullptr;
@@ -409,10 +438,11 @@ int read_global(inflx_model* m, const char* sym, T* dst, size_t bytes, bool exac
 // Put `count` doubles of parameters where kernels enqueued on `s` can read them; *d_params is the device
 // address.  A sweep re-launches with the same rows far more often than it changes them: when the current
 // slot already holds these values for this stream nothing is uploaded.
-// Ordering rule of the ring: a slot is released (release_params) on the stream of the LAST kernel that reads it -- params_reader(),
-// asked after evaluates_on_side_stream has decided where the sweep's tables go -- and is refilled only once that stream has passed
-// the release.  Released on any other stream, the slot looks free while its reader is still queued (behind other work on a
-// caller's stream), and four uploads later the reader evaluates another call's parameters.
+// Ordering rule of the ring: a slot is filled on the sweep's SweepPlan::upload_stream and released (release_params) on its
+// SweepPlan::reader_stream -- the stream of the LAST kernel that reads it -- and is refilled only once that stream has passed the
+// release.  Both come out of the one plan the entry point built for the sweep.  Released on any other stream, the slot looks free
+// while its reader is still queued (behind other work on a caller's stream), and four uploads later the reader evaluates another
+// call's parameters.
 int acquire_params(inflx_model* m, const double* p, size_t count, hipStream_t s, const double** d_params) {
   inflx_model::ParamSlot& cur = m->pslot[m->pcur];
   if (cur.dev && cur.count == count && cur.stream == s && memcmp(cur.host, p, count * sizeof(double)) == 0) {
@@ -627,7 +657,7 @@ int need_groups(inflx_model* m, uint32_t mask) {
 }
 
 // validate_lib + validiate_p (src/anguelova.rs:55-79) and the Hesse2D guard (hesse_bindings.rs:203)
-int validate(const inflx_model* m, int op, const double* p, size_t P, size_t n_p, bool kernels = true) {
+int validate(inflx_model* m, int op, const double* p, size_t P, size_t n_p, bool kernels = true) {
   if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
   if (op < 0 || op >= INFLX_OP_COUNT) return fail(INFLX_ERR_ARG, "unknown sweep operation %d", op);
   if (m->dim != 2)
@@ -639,161 +669,103 @@ int validate(const inflx_model* m, int op, const double* p, size_t P, size_t n_p
   if (P == 0) return fail(INFLX_ERR_SHAPE, "parameter array has no rows");
   // the kernels of this operation (loaded on first use when the artefact is a core object)
   if (kernels && (m->groups & group_of_op(op)) == 0) {
-    inflx_model* mm = const_cast<inflx_model*>(m);
-    INFLX_SERIALISE(mm);
-    return need_groups(mm, group_of_op(op));
+    INFLX_SERIALISE(m);
+    return need_groups(m, group_of_op(op));
   }
   return INFLX_OK;
 }
 
-int ensure_row_table(inflx_model* m, int b, size_t doubles) {
-  if (doubles <= m->d_row_table_cap[b]) return INFLX_OK;
-  // a larger table is needed: nothing may still be using the old one
-  HIP_TRY(hipDeviceSynchronize());
-  if (m->d_row_table[b]) HIP_TRY(hipFree(m->d_row_table[b]));
-  m->d_row_table[b] = nullptr;
-  m->d_row_table_cap[b] = 0;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_row_table[b]), doubles * sizeof(double)));
-  m->d_row_table_cap[b] = doubles;
-  return INFLX_OK;
-}
+// ---- what is decided per sweep, once --------------------------------------------------------------------------------------
+// Which of the four paths a sweep takes, how it is cut into batches and launches, and on which streams its kernels read the
+// parameters.  The entry point that enqueues the sweep builds one plan (plan_sweep) and hands it to acquire_params, launch_grid
+// and release_params; inflx_sweep_plan reports the same value.
+struct SweepPlan {
+  int path = INFLX_PATH_TILE;  // inflx_path
+  // Parameter rows per table batch.  Broadcast paths: one batch = evaluation + store stream; tile path: parameter rows per launch.
+  size_t batch = 0;
+  size_t cpr = 0;              // row stream: workgroups (4 KiB pieces) per grid row
+  size_t replicas = 0;         // row stream: copies of every row's table entry, a power of two
+  size_t rows_per_launch = 0;  // tile path: grid rows per launch (at most 65535 tiles, grid.y)
+  // The whole sweep runs on the caller's stream: its tables (per-row / per-column values, stage tables) are evaluated there, in
+  // front of the kernel that reads them -- no second stream, no event between the two.  Otherwise they are evaluated on the side
+  // stream, under the kernels of the launch before.
+  bool one_stream = false;
 
-// does this sweep take the two-launch row-broadcast path (per-row evaluation + store stream)?
-bool takes_row_stream(const inflx_model* m, int op, int layout, size_t P, size_t N1) {
-  if ((m->info.out_mask & 2u) != 0 || op == INFLX_OP_QDIF || (m->call_flags & INFLX_SWEEP_FORCE_TILE)) return false;
-  const bool aos6 = kOpWidth[op] == 6 && layout == INFLX_AOS;
-  (void)P;  // the path never depends on the number of parameter rows: they are batched (row_stream_plan)
-  const bool planes = (layout == INFLX_SOA || kOpWidth[op] == 1) && N1 % 2 == 0;
-  return aos6 || planes;
-}
+  // The stream the parameters are uploaded on = the stream of the first kernel that reads them: the table evaluation of the
+  // broadcast and tile paths; the fallback row kernel of row-only models reads them on the caller's stream `s`.
+  hipStream_t upload_stream(const inflx_model* m, hipStream_t s) const {
+    return path == INFLX_PATH_ROWS || one_stream ? s : m->side;
+  }
+  // ... and the stream of the LAST kernel that reads them.  The tile kernels read the parameter rows too (the point stage uses
+  // args[k]), after the table kernel, and the fallback row kernel reads them itself: `s`.  The store streams of the broadcast
+  // paths do not: there the last reader is the per-row / per-column evaluation.
+  hipStream_t reader_stream(const inflx_model* m, hipStream_t s) const {
+    return path == INFLX_PATH_ROW_STREAM || path == INFLX_PATH_COL_STREAM ? upload_stream(m, s) : s;
+  }
+};
 
-// does this sweep take the two-launch column-broadcast path (row image + copy stream)?  No model value depends on
-// x[0], and an output row is a whole number of 16-byte units.
-bool takes_col_stream(const inflx_model* m, int op, int layout, size_t P, size_t N1) {
-  if ((m->info.out_mask & 3u) != 2u || op == INFLX_OP_QDIF || (m->call_flags & INFLX_SWEEP_FORCE_TILE)) return false;
+// `alone`: the sweep is enqueued on its own at a handle that has nothing running (a host-result call that is one launch + one
+// copy, a device-result call at an idle handle).  Such a sweep has nothing to overlap its table evaluation with, and the hop
+// between two streams (event record, wait, a second doorbell) is 10-15 us of the ~60 us a small sweep takes: if it is a single
+// pair of launches, both run on the caller's stream.  Sweeps that are enqueued back to back -- the chunk pipeline, the timed
+// repetitions, a call that arrives while its predecessor runs -- keep the tables on the side stream, where the table kernel of
+// sweep k+1 overlaps the dominant kernel of sweep k like the launches of a multi-launch sweep do.
+SweepPlan plan_sweep(const InflxKernelInfo& info, int op, int layout, size_t P, size_t N1, size_t row_count, unsigned flags, bool alone) {
+  SweepPlan pl;
   const size_t K = kOpWidth[op];
+  const bool aos6 = K == 6 && layout == INFLX_AOS;
   const bool planes = layout == INFLX_SOA || K == 1;
-  (void)P;  // batched in launch_col_stream
-  if (planes) return N1 % 2 == 0;
-  return (K * N1) % 2 == 0;
-}
-
-// Geometry of the two-launch row-broadcast path for one call (shared by launch_grid and inflx_sweep_plan).
-struct RowStreamPlan {
-  size_t cpr;       // workgroups (4 KiB pieces) per grid row
-  size_t replicas;  // copies of every row's table entry, a power of two
-  size_t batch;     // parameter rows per table batch
-};
-RowStreamPlan row_stream_plan(const inflx_model* m, int op, int layout, size_t P, size_t N1, size_t row_count) {
-  const bool aos6 = kOpWidth[op] == 6 && layout == INFLX_AOS;
-  const size_t units_row = aos6 ? 3 * N1 : N1 / 2;
-  RowStreamPlan r;
-  r.cpr = (units_row + m->info.row_chunk_units - 1) / m->info.row_chunk_units;
-  // replicas of every row's table entry (see inflx_kernel_abi.h); a power of two (the evaluation
-  // kernel indexes with shifts), fewer for short rows
-  r.replicas = 32;
-  while (r.replicas > 1 && r.replicas > r.cpr) r.replicas /= 2;
-  // The table has to stay in the 256 MiB Infinity Cache between its evaluation and its use (a table
-  // fetch from HBM throttles the store stream from 6.6 to 5.0 TB/s, measured at P = 16): parameter
-  // rows are processed in batches whose table is at most 64 MiB, each batch = evaluation + stream,
-  // and the double-buffered side stream overlaps the evaluation of batch k+1 with the stream of batch k.
-  const size_t line_bytes = row_count * r.replicas * 64;
-  r.batch = std::max<size_t>(1, std::min<size_t>(P, (size_t(64) << 20) / std::max<size_t>(line_bytes, 1)));
-  r.batch = std::min<size_t>(r.batch, 65535 / (aos6 ? 1 : kOpWidth[op]));  // grid.z of the store stream = batch x planes
-  return r;
-}
-
-// Parameter rows per table batch of the column-broadcast path (images of at most 64 MiB, grid.z of the copy stream).
-size_t col_stream_batch(int op, int layout, size_t P, size_t N1) {
-  const size_t K = kOpWidth[op];
-  const size_t images_per_p = (layout == INFLX_SOA || K == 1) ? K : 1;
-  size_t batch = std::max<size_t>(1, std::min<size_t>(P, (size_t(64) << 20) / std::max<size_t>(K * N1 * 8, 1)));
-  return std::min<size_t>(batch, 65535 / images_per_p);
-}
-
-// The tile path as a sequence of launches: parameter rows in batches whose tables fit 1 GiB, grid rows in slabs of at most
-// 65535 tiles (grid.y).
-struct TilePlan {
-  size_t rows_per_launch, pbatch;
-};
-TilePlan tile_plan(const inflx_model* m, size_t P, size_t N1, size_t row_count) {
-  const size_t nu = std::max<size_t>(m->info.n_uniform, 1), nc = std::max<size_t>(m->info.n_col, 1);
-  const size_t nr = (std::max<size_t>(m->info.n_row, 1) + 1) & ~size_t(1);  // even stride of a row's values (kNRs of the kernels)
-  TilePlan t;
-  t.rows_per_launch = size_t(65535) * m->info.tile_rows;
-  const size_t per_p = nu + std::min(t.rows_per_launch, row_count) * nr + nc * N1;  // doubles per parameter row
-  t.pbatch = std::max<size_t>(1, std::min<size_t>(P, (size_t(1) << 27) / std::max<size_t>(per_p, 1)));
-  return t;
-}
-// Which stream are the parameters uploaded on?  The first kernel that reads them runs on the side stream for the two
-// broadcast paths (per-row / per-column evaluation) and for the tile path (stage tables) -- unless the sweep is a single
-// pair of launches enqueued alone (below) --; the fallback row kernel of row-only models reads them on the caller's stream.
-// `alone`: the sweep is enqueued on its own and waited for (a host-result call that is one launch + one copy).  Sweeps that may be
-// enqueued back to back -- the asynchronous device-result entry points, the chunk pipeline -- keep the tables on the side stream, where
-// the table kernel of sweep k+1 overlaps the tile kernel of sweep k like the launches of a multi-launch sweep do.
-bool evaluates_on_side_stream(inflx_model* m, int op, int layout, size_t P, size_t N1, size_t row_count, bool alone = false) {
-  m->tables_on_callers_stream = false;
-  // the broadcast paths: per-row / per-column evaluation, then the store stream; one table batch = one pair of launches
-  if (takes_row_stream(m, op, layout, P, N1)) {
-    m->tables_on_callers_stream = alone && P <= row_stream_plan(m, op, layout, P, N1, row_count).batch;
-    return !m->tables_on_callers_stream;
+  // a model that ignores a grid axis is evaluated along the other one only -- except by the flag sweep, which reads the basis
+  // vector, whose axis dependence the out_mask does not describe, and by INFLX_SWEEP_FORCE_TILE
+  const bool may_broadcast = op != INFLX_OP_QDIF && !(flags & INFLX_SWEEP_FORCE_TILE);
+  const bool row_only = may_broadcast && (info.out_mask & 2u) == 0, col_only = may_broadcast && (info.out_mask & 3u) == 2u;
+  if (row_only && (aos6 || (planes && N1 % 2 == 0))) {
+    // two launches: per-row evaluation + store stream.  (The path never depends on P: parameter rows are batched.)
+    pl.path = INFLX_PATH_ROW_STREAM;
+    const size_t units_row = aos6 ? 3 * N1 : N1 / 2;
+    pl.cpr = (units_row + info.row_chunk_units - 1) / info.row_chunk_units;
+    // replicas of every row's table entry (see inflx_kernel_abi.h); a power of two (the evaluation
+    // kernel indexes with shifts), fewer for short rows
+    pl.replicas = 32;
+    while (pl.replicas > 1 && pl.replicas > pl.cpr) pl.replicas /= 2;
+    // The table has to stay in the 256 MiB Infinity Cache between its evaluation and its use (a table
+    // fetch from HBM throttles the store stream from 6.6 to 5.0 TB/s, measured at P = 16): parameter
+    // rows are processed in batches whose table is at most 64 MiB, each batch = evaluation + stream,
+    // and the double-buffered side stream overlaps the evaluation of batch k+1 with the stream of batch k.
+    const size_t line_bytes = row_count * pl.replicas * 64;
+    pl.batch = std::max<size_t>(1, std::min<size_t>(P, (size_t(64) << 20) / std::max<size_t>(line_bytes, 1)));
+    pl.batch = std::min<size_t>(pl.batch, 65535 / (aos6 ? 1 : K));  // grid.z of the store stream = batch x planes
+    pl.one_stream = alone && P <= pl.batch;
+  } else if (col_only && (planes ? N1 : K * N1) % 2 == 0) {
+    // two launches: row image + copy stream.  No model value depends on x[0], and an output row is a whole number of 16-byte
+    // units; images of at most 64 MiB per batch, grid.z of the copy stream = batch x images per parameter row
+    pl.path = INFLX_PATH_COL_STREAM;
+    pl.batch = std::max<size_t>(1, std::min<size_t>(P, (size_t(64) << 20) / std::max<size_t>(K * N1 * 8, 1)));
+    pl.batch = std::min<size_t>(pl.batch, 65535 / (planes ? K : 1));
+    pl.one_stream = alone && P <= pl.batch;
+  } else if (row_only) {
+    pl.path = INFLX_PATH_ROWS;  // result shapes the store streams do not cover: per-row evaluation inside the kernel
+  } else {
+    // a sequence of launches: parameter rows in batches whose tables fit 1 GiB, grid rows in slabs of at most 65535 tiles
+    pl.path = INFLX_PATH_TILE;
+    const size_t nu = std::max<size_t>(info.n_uniform, 1), nc = std::max<size_t>(info.n_col, 1);
+    const size_t nr = (std::max<size_t>(info.n_row, 1) + 1) & ~size_t(1);  // even stride of a row's values (kNRs of the kernels)
+    pl.rows_per_launch = size_t(65535) * info.tile_rows;
+    const size_t per_p = nu + std::min(pl.rows_per_launch, row_count) * nr + nc * N1;  // doubles per parameter row
+    pl.batch = std::max<size_t>(1, std::min<size_t>(P, (size_t(1) << 27) / std::max<size_t>(per_p, 1)));
+    pl.one_stream = alone && P <= pl.batch && row_count <= pl.rows_per_launch;
   }
-  if (takes_col_stream(m, op, layout, P, N1)) {
-    m->tables_on_callers_stream = alone && P <= col_stream_batch(op, layout, P, N1);
-    return !m->tables_on_callers_stream;
-  }
-  const bool row_uniform = (m->info.out_mask & 2u) == 0 && op != INFLX_OP_QDIF && !(m->call_flags & INFLX_SWEEP_FORCE_TILE);
-  if (row_uniform) return false;
-  // tile path: tables, then tile kernel.  Several launches: the tables of launch k+1 are built on the side stream while the tile
-  // kernel of launch k runs.  A single launch that nothing follows has nothing to overlap with, and the hop between two streams
-  // (event record, wait, a second doorbell) is 10-15 us of the ~60 us a small sweep takes: it runs on the caller's stream alone.
-  const TilePlan t = tile_plan(m, P, N1, row_count);
-  m->tables_on_callers_stream = alone && P <= t.pbatch && row_count <= t.rows_per_launch;
-  // (experiments, scripts/tables_policy_probe.py: "same" = the tables of every single-launch sweep on the caller's stream, "side" = never)
-  static const int forced = [] {
-    const char* e = getenv("INFLX_EXPERIMENT_TABLES");
-    return !e ? 0 : (strcmp(e, "same") == 0 ? 1 : (strcmp(e, "side") == 0 ? 2 : 0));
-  }();
-  if (forced == 1) m->tables_on_callers_stream = P <= t.pbatch && row_count <= t.rows_per_launch;
-  if (forced == 2) m->tables_on_callers_stream = false;
-  return !m->tables_on_callers_stream;
-}
-// ... and on which stream does the LAST kernel that reads them run?  The tile kernels read the parameter rows too
-// (the point stage uses args[k]), after the table kernel, and the fallback row kernel reads them itself: the caller's stream `s`.
-// On the broadcast paths the store streams do not: the last reader is the per-row / per-column evaluation, on the stream
-// evaluates_on_side_stream chose for it (the caller's for a lone sweep, the side stream otherwise).  Call it after that decision.
-hipStream_t params_reader(const inflx_model* m, int op, int layout, size_t P, size_t N1, hipStream_t s) {
-  if (takes_row_stream(m, op, layout, P, N1) || takes_col_stream(m, op, layout, P, N1)) return m->tables_on_callers_stream ? s : m->side;
-  return s;
+  return pl;
 }
 
-// Has every kernel this handle enqueued earlier finished?  A sweep that arrives at an idle handle has nothing to overlap its
-// table evaluation with: it is enqueued as `alone` (tables in front of the tile kernel on the caller's stream, no second stream, no
-// event hop).  One that arrives while the previous sweep's kernels are still running keeps the side stream, where its tables are
+// Has every kernel this handle enqueued earlier finished?  A sweep that arrives at an idle handle is planned as `alone`
+// (plan_sweep); one that arrives while the previous sweep's kernels are still running keeps the side stream, where its tables are
 // evaluated under them.  (A user's lone call and the back-to-back calls of a scan both get the shorter of the two shapes.)
 bool handle_idle(inflx_model* m) {
-  bool idle = true;
-  for (int b = 0; b < 2 && idle; ++b) {
-    if (m->stage_used[b] && hipEventQuery(m->stage_free[b]) != hipSuccess) idle = false;
-    if (m->table_used[b] && hipEventQuery(m->table_free[b]) != hipSuccess) idle = false;
-  }
+  const bool idle = m->row_ring.idle() && m->stage_ring.idle();
   (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure
   return idle;
 }
-
-// the inflx_sweep_flags of an *_ex call, for as long as it holds the handle's lock
-struct FlagScope {
-  inflx_model* m;
-  unsigned before;
-  FlagScope(inflx_model* m_, unsigned flags) : m(m_), before(m_ ? m_->call_flags : 0u) {
-    if (m) m->call_flags = flags;
-  }
-  ~FlagScope() {
-    if (m) m->call_flags = before;
-  }
-  FlagScope(const FlagScope&) = delete;
-  FlagScope& operator=(const FlagScope&) = delete;
-};
 
 // (in-pipeline timing of the dominant kernel, see inflx_model::probe) -- no-ops unless a probe is armed and has pairs left
 hipError_t probe_begin(inflx_model* m, hipStream_t s) {
@@ -811,106 +783,63 @@ hipError_t probe_end(inflx_model* m, hipStream_t s) {
 
 // ---- the four ways a sweep is enqueued; `a` arrives with the grid geometry filled in (launch_grid) -------------------
 
-// Row-broadcast path: per-row values into the row table on the side stream, then the broadcast store stream on `s`
-// (one 16-byte store per thread, 4 KiB per workgroup).  `what`: 0 = both, 1 = only the evaluation, 2 = only the
-// store stream (used to time the dominant kernel on its own).
-int launch_row_stream(inflx_model* m, int op, InflxSweepArgs a, const double* d_params, size_t P, double* d_out, size_t N1, size_t row_count, int layout, hipStream_t s, int what, double* d_stats) {
+// What tells the two broadcast paths apart (launch_grid fills it in); the protocol is launch_broadcast's.
+struct BroadcastPath {
+  hipFunction_t eval;     // writes the table: per-row values / the image of one output row
+  unsigned eval_gx, eval_block;
+  hipFunction_t store;    // streams the table into the result (one 16-byte store per thread, 4 KiB per workgroup)
+  size_t cpr;             // its workgroups per grid row
+  size_t z_per_p;         // its grid.z per parameter row (planes / images)
+  size_t table_doubles;   // table doubles per parameter row
+};
+
+// The broadcast paths: the table of one batch of parameter rows is evaluated on the side stream (on the caller's for a
+// single pair of launches enqueued alone), then the store stream runs on `s`.  `stores_only`: only the store streams, from
+// whatever the tables hold (used to time the dominant kernel on its own).
+int launch_broadcast(inflx_model* m, const SweepPlan& plan, const BroadcastPath& path, int op, InflxSweepArgs a, const double* d_params, size_t P,
+                     double* d_out, hipStream_t s, bool stores_only) {
   void* params[] = {&a};
-  const bool aos6 = kOpWidth[op] == 6 && layout == INFLX_AOS;
-  hipStream_t ev = m->tables_on_callers_stream ? s : m->side;  // (decided with the stream of the parameter upload, evaluates_on_side_stream)
-  const RowStreamPlan plan = row_stream_plan(m, op, layout, P, N1, row_count);
-  const size_t cpr = plan.cpr, replicas = plan.replicas, batch = plan.batch;
-  if (cpr > 0x7fffffffULL) return fail(INFLX_ERR_SHAPE, "grid rows too long for one launch");
-  const size_t K = kOpWidth[op];
+  TableRing& ring = m->row_ring;
+  const hipStream_t ev = plan.upload_stream(m, s);
+  const size_t batch = plan.batch, row_count = a.row_count;
+  if (path.cpr > 0x7fffffffULL) return fail(INFLX_ERR_SHAPE, "grid rows too long for one launch");
   // the timing-only mode re-runs store streams from the table of the sweep before it, and only the last
   // batch's table is still there
-  if (what == 2 && batch < P)
+  if (stores_only && batch < P)
     return fail(INFLX_ERR_ARG, "dominant_only timing needs the parameter rows to fit one table batch (%zu rows here, got %zu)", batch, P);
+  const bool store = d_out != nullptr;
   for (size_t p0 = 0; p0 < P; p0 += batch) {
     const size_t pb = std::min(batch, P - p0);
-    // `what` == 2 (timing only) re-runs the store streams from whatever the tables hold
-    const int b = what == 2 ? (int)((m->table_turn + 1) & 1) : (int)(m->table_turn & 1);
-    const bool store = d_out != nullptr;
-    int rc = store ? ensure_row_table(m, b, pb * row_count * replicas * 8) : INFLX_OK;
-    if (rc) return rc;
-    a.params = d_params + p0 * m->n_par;
-    a.out = store ? d_out + p0 * row_count * N1 * K : nullptr;  // same offset for [P][rows][N1][K] and [P][K][rows][N1]
-    a.P = (uint32_t)pb;
-    a.row_table = store ? m->d_row_table[b] : nullptr;
-    a.table_replicas = (uint32_t)replicas;
-    a.stream_planes = (uint32_t)K;
-    if (what != 2) {
-      // per-row evaluation on the side stream (on the caller's for a single pair of launches enqueued alone), as soon as the
-      // previous reader of this table is done
-      if (m->table_used[b]) HIP_TRY(hipStreamWaitEvent(ev, m->table_free[b], 0));
-      HIP_TRY(hipModuleLaunchKernel(d_stats ? m->rowvals_stats : m->rowvals[op], (unsigned)((row_count + 63) / 64), (unsigned)pb, 1, 64, 1, 1, 0,
-                                    ev, params, nullptr));
-      if (ev != s) HIP_TRY(hipEventRecord(m->table_ready[b], ev));
-      m->table_turn++;
+    const int b = (int)((ring.turn + (stores_only ? 1 : 0)) & 1);  // (timing only: the buffer the sweep before it filled)
+    if (store && pb * path.table_doubles > ring.cap[b]) {
+      // a larger table is needed: nothing may still be using the old one
+      HIP_TRY(hipDeviceSynchronize());
+      const int rc = ring.grow(b, pb * path.table_doubles);
+      if (rc) return rc;
     }
-    if (what != 1 && store) {
-      if (ev != s) HIP_TRY(hipStreamWaitEvent(s, m->table_ready[b], 0));
+    a.params = d_params + p0 * m->n_par;
+    a.out = store ? d_out + p0 * row_count * a.N1 * kOpWidth[op] : nullptr;  // same offset for [P][rows][N1][K] and [P][K][rows][N1]
+    a.P = (uint32_t)pb;
+    a.row_table = store ? ring.buf[b] : nullptr;
+    if (!stores_only) {
+      // the evaluation, as soon as the previous reader of this table is done
+      if (ring.used[b]) HIP_TRY(hipStreamWaitEvent(ev, ring.free[b], 0));
+      HIP_TRY(hipModuleLaunchKernel(path.eval, path.eval_gx, (unsigned)pb, 1, path.eval_block, 1, 1, 0, ev, params, nullptr));
+      if (ev != s) HIP_TRY(hipEventRecord(ring.ready[b], ev));
+      ring.turn++;
+    }
+    if (store) {
+      if (ev != s) HIP_TRY(hipStreamWaitEvent(s, ring.ready[b], 0));
       // grid.y is limited to 65535, longer slabs take several launches
       for (size_t r0 = 0; r0 < row_count; r0 += 65535) {
         a.stream_row0 = (uint32_t)r0;
         const size_t nr = std::min<size_t>(65535, row_count - r0);
         HIP_TRY(probe_begin(m, s));
-        HIP_TRY(hipModuleLaunchKernel(aos6 ? m->rowstream6 : m->rowstream_planes, (unsigned)cpr, (unsigned)nr,
-                                      (unsigned)(aos6 ? pb : pb * K), m->info.tile_cols, 1, 1, 0, s, params, nullptr));
+        HIP_TRY(hipModuleLaunchKernel(path.store, (unsigned)path.cpr, (unsigned)nr, (unsigned)(pb * path.z_per_p), m->info.tile_cols, 1, 1, 0, s, params, nullptr));
         HIP_TRY(probe_end(m, s));
       }
-      HIP_TRY(hipEventRecord(m->table_free[b], s));
-      m->table_used[b] = true;
-    }
-  }
-  return INFLX_OK;
-}
-
-// Column-broadcast path: the image of one output row per parameter row (and plane) into the table on the side stream,
-// then the copy stream on `s`.
-int launch_col_stream(inflx_model* m, int op, InflxSweepArgs a, const double* d_params, size_t P, double* d_out, size_t N1, size_t row_count, int layout, hipStream_t s, int what, double* d_stats) {
-  void* params[] = {&a};
-  const size_t K = kOpWidth[op];
-  hipStream_t ev = m->tables_on_callers_stream ? s : m->side;
-  const bool planes = layout == INFLX_SOA || K == 1;
-  const size_t images_per_p = planes ? K : 1;
-  const size_t units = (planes ? N1 : K * N1) / 2;  // 16-byte units per output row
-  const size_t cpr = (units + m->info.tile_cols - 1) / m->info.tile_cols;
-  if (cpr > 0x7fffffffULL) return fail(INFLX_ERR_SHAPE, "grid rows too long for one launch");
-  const size_t image_doubles = K * N1;  // per parameter row
-  const size_t batch = col_stream_batch(op, layout, P, N1);
-  if (what == 2 && batch < P)
-    return fail(INFLX_ERR_ARG, "dominant_only timing needs the parameter rows to fit one table batch (%zu rows here, got %zu)", batch, P);
-  const size_t gx = (N1 + m->info.tile_cols - 1) / m->info.tile_cols;
-  for (size_t p0 = 0; p0 < P; p0 += batch) {
-    const size_t pb = std::min(batch, P - p0);
-    const int b = what == 2 ? (int)((m->table_turn + 1) & 1) : (int)(m->table_turn & 1);
-    const bool store = d_out != nullptr;
-    int rc = store ? ensure_row_table(m, b, pb * image_doubles) : INFLX_OK;
-    if (rc) return rc;
-    a.params = d_params + p0 * m->n_par;
-    a.out = store ? d_out + p0 * row_count * N1 * K : nullptr;
-    a.P = (uint32_t)pb;
-    a.row_table = store ? m->d_row_table[b] : nullptr;
-    a.stream_units = units;
-    if (what != 2) {
-      if (m->table_used[b]) HIP_TRY(hipStreamWaitEvent(ev, m->table_free[b], 0));
-      HIP_TRY(hipModuleLaunchKernel(d_stats ? m->colvals_stats : m->colvals[op], (unsigned)gx, (unsigned)pb, 1, m->info.tile_cols, 1, 1, 0, ev, params,
-                                    nullptr));
-      if (ev != s) HIP_TRY(hipEventRecord(m->table_ready[b], ev));
-      m->table_turn++;
-    }
-    if (what != 1 && store) {
-      if (ev != s) HIP_TRY(hipStreamWaitEvent(s, m->table_ready[b], 0));
-      for (size_t r0 = 0; r0 < row_count; r0 += 65535) {
-        a.stream_row0 = (uint32_t)r0;
-        const size_t nr = std::min<size_t>(65535, row_count - r0);
-        HIP_TRY(probe_begin(m, s));
-        HIP_TRY(hipModuleLaunchKernel(m->colstream, (unsigned)cpr, (unsigned)nr, (unsigned)(pb * images_per_p), m->info.tile_cols, 1, 1, 0, s, params, nullptr));
-        HIP_TRY(probe_end(m, s));
-      }
-      HIP_TRY(hipEventRecord(m->table_free[b], s));
-      m->table_used[b] = true;
+      HIP_TRY(hipEventRecord(ring.free[b], s));
+      ring.used[b] = true;
     }
   }
   return INFLX_OK;
@@ -948,24 +877,23 @@ constexpr size_t kLaunchWorkgroups = 1024;  // workgroups a tile launch is cut i
 // 0.167 ms instead of 0.130).  The height is therefore what gives the launch about 1024 workgroups, between 1 row and half the
 // full height; half-height tiles then stay until they number 4096 (a launch of two to four rounds of full-height workgroups ends
 // with a ragged last round: 4096 x 4096 is 2.7), and large launches have the full height and its amortisation of the per-tile
-// prologue (scripts/tile_rows_probe.py, profiles/r04_experiments.txt section 17).
+// prologue (profiles/r04_experiments.txt section 17).
 size_t tile_height(size_t full, size_t segments) {
   return std::min(full, std::max<size_t>({size_t(1), std::min(full / 2, segments / kLaunchWorkgroups), segments / (4 * kLaunchWorkgroups)}));
 }
 
-int launch_tiles(inflx_model* m, int op, InflxSweepArgs a, const double* d_params, size_t P, double* d_out, size_t N1, size_t row_count, hipStream_t s,
-                 double* d_stats) {
+int launch_tiles(inflx_model* m, const SweepPlan& plan, int op, InflxSweepArgs a, const double* d_params, size_t P, double* d_out, size_t N1,
+                 size_t row_count, hipStream_t s, double* d_stats) {
   void* params[] = {&a};
+  TableRing& ring = m->stage_ring;
   const size_t gx = (N1 + m->info.tile_cols - 1) / m->info.tile_cols;
   if (gx > 0x7fffffffULL) return fail(INFLX_ERR_SHAPE, "grid rows too long for one launch (%zu column tiles)", gx);
   if (row_count > 0xffffffffULL) return fail(INFLX_ERR_SHAPE, "at most 2^32 grid rows per call (got %zu)", row_count);
   hipFunction_t f = d_stats ? (d_out ? m->tile_stats : m->tile_stats_nostore) : m->tile[op];
   const size_t nu = std::max<size_t>(m->info.n_uniform, 1), nc = std::max<size_t>(m->info.n_col, 1);
   const size_t nr = (std::max<size_t>(m->info.n_row, 1) + 1) & ~size_t(1);  // even stride of a row's values (kNRs of the kernels)
-  const TilePlan plan = tile_plan(m, P, N1, row_count);
-  const size_t rows_per_launch = plan.rows_per_launch, pbatch = plan.pbatch;
-  // (the entry point decided where the tables are built when it chose the stream of the parameter upload: the two must agree)
-  hipStream_t tables = m->tables_on_callers_stream ? s : m->side;
+  const size_t rows_per_launch = plan.rows_per_launch, pbatch = plan.batch;
+  const hipStream_t tables = plan.upload_stream(m, s);
   for (size_t p0 = 0; p0 < P; p0 += pbatch) {
     const size_t pb = std::min(pbatch, P - p0);
     a.params = d_params + p0 * m->n_par;
@@ -974,64 +902,52 @@ int launch_tiles(inflx_model* m, int op, InflxSweepArgs a, const double* d_param
     for (size_t r0 = 0; r0 < row_count; r0 += rows_per_launch) {
       const size_t slab = std::min(rows_per_launch, row_count - r0);
       const size_t need = pb * (nu + slab * nr + nc * N1);
-      const int b = (int)(m->stage_turn & 1);
-      if (need > m->d_stage_tab_cap[b]) {
+      const int b = (int)(ring.turn & 1);
+      if (need > ring.cap[b]) {
         // nothing may still be reading the old tables
-        if (m->stage_used[b]) HIP_TRY(hipEventSynchronize(m->stage_free[b]));
-        if (m->d_stage_tab[b]) HIP_TRY(hipFree(m->d_stage_tab[b]));
-        m->d_stage_tab[b] = nullptr;
-        m->d_stage_tab_cap[b] = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_stage_tab[b]), need * sizeof(double)));
-        m->d_stage_tab_cap[b] = need;
+        if (ring.used[b]) HIP_TRY(hipEventSynchronize(ring.free[b]));
+        const int rc = ring.grow(b, need);
+        if (rc) return rc;
       }
-      a.row_table = m->d_stage_tab[b];
+      a.row_table = ring.buf[b];
       a.stream_row0 = (uint32_t)r0;
       a.stream_units = slab;
       // tables on the side stream, as soon as the tile kernel that read this buffer two launches ago is done ...
-      if (m->stage_used[b]) HIP_TRY(hipStreamWaitEvent(tables, m->stage_free[b], 0));
+      if (ring.used[b]) HIP_TRY(hipStreamWaitEvent(tables, ring.free[b], 0));
       const size_t tx = (slab + m->info.tile_cols - 1) / m->info.tile_cols + (N1 + m->info.tile_cols - 1) / m->info.tile_cols;  // row blocks, then column blocks
       HIP_TRY(hipModuleLaunchKernel(m->stage_tables, (unsigned)tx, (unsigned)pb, 1, m->info.tile_cols, 1, 1, 0, tables, params, nullptr));
-      m->stage_turn++;
+      ring.turn++;
       // ... and the tile kernel on the caller's stream behind them
       if (tables != s) {
-        HIP_TRY(hipEventRecord(m->stage_ready[b], tables));
-        HIP_TRY(hipStreamWaitEvent(s, m->stage_ready[b], 0));
+        HIP_TRY(hipEventRecord(ring.ready[b], tables));
+        HIP_TRY(hipStreamWaitEvent(s, ring.ready[b], 0));
       }
-      const size_t full = m->info.tile_rows;
-      size_t th = tile_height(full, gx * slab * pb);
-      // (experiments, scripts/tile_rows_probe.py: a height forced through the environment -- looked at per launch only if the variable
-      // existed when the first sweep ran, so that ordinary processes never read the environment while other threads may be writing it)
-      static const bool forced = getenv("INFLX_EXPERIMENT_TILE_ROWS") != nullptr;
-      if (forced) {
-        const char* e = getenv("INFLX_EXPERIMENT_TILE_ROWS");
-        const int rows = e ? atoi(e) : 0;
-        if (rows > 0) th = std::min<size_t>(full, (size_t)rows);
-      }
+      const size_t th = tile_height(m->info.tile_rows, gx * slab * pb);
       a.tile_rows = (uint32_t)th;
       const size_t gy = (slab + th - 1) / th;
       HIP_TRY(probe_begin(m, s));
       HIP_TRY(hipModuleLaunchKernel(f, (unsigned)gx, (unsigned)gy, (unsigned)pb, m->info.tile_cols, 1, 1, 0, s, params, nullptr));
       HIP_TRY(probe_end(m, s));
-      HIP_TRY(hipEventRecord(m->stage_free[b], s));
-      m->stage_used[b] = true;
+      HIP_TRY(hipEventRecord(ring.free[b], s));
+      ring.used[b] = true;
     }
   }
   return INFLX_OK;
 }
 
-// Enqueue one sweep on `s`; `d_params` points at P parameter rows in device memory.
-// `what`: 0 = the whole sweep; for the two-launch broadcast paths 1 = only the evaluation,
-// 2 = only the store stream (used to time the dominant kernel on its own).
-int launch_grid(inflx_model* m, int op, const double* d_params, size_t P, double* d_out, const double* ss, size_t N0, size_t N1,
-                size_t row_begin, size_t row_count, int layout, hipStream_t s, int what = 0, double accuracy = 0.0,
+// Enqueue one sweep on `s` the way `plan` says; `d_params` points at P parameter rows in device memory.
+// `stores_only`: of the two-launch broadcast paths only the store stream (used to time the dominant kernel on its own).
+int launch_grid(inflx_model* m, const SweepPlan& plan, int op, const double* d_params, size_t P, double* d_out, const double* ss, size_t N0,
+                size_t N1, size_t row_begin, size_t row_count, int layout, hipStream_t s, bool stores_only = false, double accuracy = 0.0,
                 double* d_stats = nullptr) {
   if (row_count == 0 || N1 == 0) return INFLX_OK;
   if (P > 65535) {
-    // grid.z (and grid.y of the evaluation kernels) carries the parameter row: longer parameter axes take several launches
+    // grid.z (and grid.y of the evaluation kernels) carries the parameter row: longer parameter axes take several launches,
+    // under the plan of the whole call (its batches never exceed 65535 rows on the broadcast paths, and the streams stay)
     for (size_t p0 = 0; p0 < P; p0 += 65535) {
       const size_t pb = std::min<size_t>(65535, P - p0);
       double* sub = d_out ? reinterpret_cast<double*>(reinterpret_cast<char*>(d_out) + p0 * row_count * N1 * kOpBytes[op]) : nullptr;
-      const int rc = launch_grid(m, op, d_params + p0 * m->n_par, pb, sub, ss, N0, N1, row_begin, row_count, layout, s, what, accuracy, d_stats);
+      const int rc = launch_grid(m, plan, op, d_params + p0 * m->n_par, pb, sub, ss, N0, N1, row_begin, row_count, layout, s, stores_only, accuracy, d_stats);
       if (rc) return rc;
     }
     return INFLX_OK;
@@ -1053,12 +969,31 @@ int launch_grid(inflx_model* m, int op, const double* d_params, size_t P, double
   a.col_chunks = 1;
   a.accuracy = accuracy;
   a.stats = d_stats;  // non-NULL: complete_analysis with the running summary (d_out may then be NULL)
-  if (takes_row_stream(m, op, layout, P, N1)) return launch_row_stream(m, op, a, d_params, P, d_out, N1, row_count, layout, s, what, d_stats);
-  if (takes_col_stream(m, op, layout, P, N1)) return launch_col_stream(m, op, a, d_params, P, d_out, N1, row_count, layout, s, what, d_stats);
-  // the flag sweep reads the basis vector, whose axis dependence the out_mask does not describe
-  const bool row_uniform = (m->info.out_mask & 2u) == 0 && op != INFLX_OP_QDIF && !(m->call_flags & INFLX_SWEEP_FORCE_TILE);
-  if (row_uniform) return launch_rows_fallback(m, op, a, P, N1, row_count, s);
-  return launch_tiles(m, op, a, d_params, P, d_out, N1, row_count, s, d_stats);
+  const size_t K = kOpWidth[op];
+  switch (plan.path) {
+    case INFLX_PATH_ROW_STREAM: {
+      // per-row values [P][rows][replicas][8] into the table, then the broadcast store stream
+      const bool aos6 = K == 6 && layout == INFLX_AOS;
+      a.table_replicas = (uint32_t)plan.replicas;
+      a.stream_planes = (uint32_t)K;
+      const BroadcastPath path = {d_stats ? m->rowvals_stats : m->rowvals[op], (unsigned)((row_count + 63) / 64), 64,
+                                  aos6 ? m->rowstream6 : m->rowstream_planes, plan.cpr, aos6 ? 1 : K, row_count * plan.replicas * 8};
+      return launch_broadcast(m, plan, path, op, a, d_params, P, d_out, s, stores_only);
+    }
+    case INFLX_PATH_COL_STREAM: {
+      // the image of one output row per parameter row (and plane) into the table, then the copy stream
+      const bool planes = layout == INFLX_SOA || K == 1;
+      a.stream_units = (planes ? N1 : K * N1) / 2;  // 16-byte units per output row
+      const size_t tc = m->info.tile_cols;
+      const BroadcastPath path = {d_stats ? m->colvals_stats : m->colvals[op], (unsigned)((N1 + tc - 1) / tc), (unsigned)tc,
+                                  m->colstream, (a.stream_units + tc - 1) / tc, planes ? K : 1, K * N1};
+      return launch_broadcast(m, plan, path, op, a, d_params, P, d_out, s, stores_only);
+    }
+    case INFLX_PATH_ROWS:
+      return launch_rows_fallback(m, op, a, P, N1, row_count, s);
+    default:
+      return launch_tiles(m, plan, op, a, d_params, P, d_out, N1, row_count, s, d_stats);
+  }
 }
 
 int ensure_chunk(inflx_model* m, int which, size_t bytes) {
@@ -1236,32 +1171,21 @@ int inflx_open(const char* artefact_path, int device, inflx_model** out) {
     if ((rc = resolve_group_kernels(m, m->module, present, artefact_path))) return bail(rc);
     m->groups = present;
   }
-  // (experiment, scripts/tables_policy_probe.py: the side stream at the highest priority the device offers)
-  int side_priority = 0;
-  if (const char* e = getenv("INFLX_EXPERIMENT_SIDE_PRIORITY")) {
-    int least = 0, greatest = 0;
-    if (atoi(e) != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) side_priority = greatest;
-  }
   if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithPriority(&m->side, hipStreamNonBlocking, side_priority) != hipSuccess ||
+      hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking) != hipSuccess) {
     fail(INFLX_ERR_DEVICE, "could not create HIP streams");
     return bail(INFLX_ERR_DEVICE);
   }
   for (int k = 0; k < 2; ++k) {
     if (hipEventCreateWithFlags(&m->chunk_done[k], hipEventDisableTiming) != hipSuccess ||
-        // ordering-only events between two streams of this device: no system-scope fence needed (the
-        // kernels' own agent-scope release/acquire at their boundaries publishes the row table)
-        hipEventCreateWithFlags(&m->table_ready[k], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
-        hipEventCreateWithFlags(&m->table_free[k], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
         hipEventCreateWithFlags(&m->copy_done[k], hipEventDisableTiming) != hipSuccess) {
       fail(INFLX_ERR_DEVICE, "could not create HIP events");
       return bail(INFLX_ERR_DEVICE);
     }
   }
-  for (int k = 0; k < 2; ++k) {
-    if (hipEventCreateWithFlags(&m->stage_ready[k], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
-        hipEventCreateWithFlags(&m->stage_free[k], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) {
+  for (TableRing* ring : {&m->row_ring, &m->stage_ring}) {
+    if (!ring->create()) {
       fail(INFLX_ERR_DEVICE, "could not create HIP events");
       return bail(INFLX_ERR_DEVICE);
     }
@@ -1285,15 +1209,8 @@ void inflx_close(inflx_model* m) {
     if (m->d_chunk[k]) (void)hipFree(m->d_chunk[k]);
     if (m->chunk_done[k]) (void)hipEventDestroy(m->chunk_done[k]);
     if (m->copy_done[k]) (void)hipEventDestroy(m->copy_done[k]);
-    if (m->table_ready[k]) (void)hipEventDestroy(m->table_ready[k]);
-    if (m->table_free[k]) (void)hipEventDestroy(m->table_free[k]);
-    if (m->d_row_table[k]) (void)hipFree(m->d_row_table[k]);
   }
-  for (int k = 0; k < 2; ++k) {
-    if (m->stage_ready[k]) (void)hipEventDestroy(m->stage_ready[k]);
-    if (m->stage_free[k]) (void)hipEventDestroy(m->stage_free[k]);
-    if (m->d_stage_tab[k]) (void)hipFree(m->d_stage_tab[k]);
-  }
+  for (TableRing* ring : {&m->row_ring, &m->stage_ring}) ring->destroy();
   if (m->t0) (void)hipEventDestroy(m->t0);
   if (m->t1) (void)hipEventDestroy(m->t1);
   if (m->sf_done) (void)hipEventDestroy(m->sf_done);
@@ -1354,34 +1271,21 @@ int inflx_sweep_plan(const inflx_model* m, int op, size_t P, size_t N1, size_t r
   return inflx_sweep_plan_ex(m, op, P, N1, row_count, layout, INFLX_SWEEP_DEFAULT, plan);
 }
 
-int inflx_sweep_plan_ex(const inflx_model* cm, int op, size_t P, size_t N1, size_t row_count, int layout, unsigned flags, uint32_t plan[4]) {
-  if (!cm || !plan) return fail(INFLX_ERR_ARG, "model handle / plan array is NULL");
+int inflx_sweep_plan_ex(const inflx_model* m, int op, size_t P, size_t N1, size_t row_count, int layout, unsigned flags, uint32_t plan[4]) {
+  if (!m || !plan) return fail(INFLX_ERR_ARG, "model handle / plan array is NULL");
   if (op < 0 || op >= INFLX_OP_COUNT) return fail(INFLX_ERR_ARG, "unknown sweep operation %d", op);
   if (flags & ~(unsigned)INFLX_SWEEP_FORCE_TILE) return fail(INFLX_ERR_ARG, "unknown sweep flags 0x%x", flags);
-  inflx_model* m = const_cast<inflx_model*>(cm);  // (the flags live in the handle for the duration of the call)
-  INFLX_SERIALISE(m);
-  FlagScope scope(m, flags);
-  plan[0] = plan[1] = plan[2] = plan[3] = 0;
-  if (takes_row_stream(m, op, layout, P, N1)) {
-    const RowStreamPlan r = row_stream_plan(m, op, layout, P, N1, row_count);
-    plan[0] = INFLX_PATH_ROW_STREAM;
-    plan[1] = (uint32_t)r.batch;
-    plan[2] = (uint32_t)((P + r.batch - 1) / r.batch);
-    plan[3] = (uint32_t)r.replicas;
-  } else if (takes_col_stream(m, op, layout, P, N1)) {
-    const size_t batch = col_stream_batch(op, layout, P, N1);
-    plan[0] = INFLX_PATH_COL_STREAM;
-    plan[1] = (uint32_t)batch;
-    plan[2] = (uint32_t)((P + batch - 1) / batch);
-  } else if ((m->info.out_mask & 2u) == 0 && op != INFLX_OP_QDIF && !(m->call_flags & INFLX_SWEEP_FORCE_TILE)) {
-    plan[0] = INFLX_PATH_ROWS;
-  } else {
-    plan[0] = INFLX_PATH_TILE;
-    const TilePlan t = tile_plan(m, P, N1, row_count);
-    const size_t gx = (N1 + m->info.tile_cols - 1) / m->info.tile_cols, slab = std::min(t.rows_per_launch, row_count);
-    plan[1] = (uint32_t)t.pbatch;
-    plan[2] = (uint32_t)(((P + t.pbatch - 1) / t.pbatch) * ((row_count + t.rows_per_launch - 1) / t.rows_per_launch));
-    plan[3] = (uint32_t)tile_height(m->info.tile_rows, gx * slab * t.pbatch);
+  const SweepPlan pl = plan_sweep(m->info, op, layout, P, N1, row_count, flags, /*alone=*/false);
+  plan[0] = (uint32_t)pl.path;
+  plan[1] = plan[2] = plan[3] = 0;
+  if (pl.path == INFLX_PATH_ROWS) return INFLX_OK;
+  plan[1] = (uint32_t)pl.batch;
+  plan[2] = (uint32_t)((P + pl.batch - 1) / pl.batch);
+  if (pl.path == INFLX_PATH_ROW_STREAM) plan[3] = (uint32_t)pl.replicas;
+  if (pl.path == INFLX_PATH_TILE) {
+    const size_t gx = (N1 + m->info.tile_cols - 1) / m->info.tile_cols, slab = std::min(pl.rows_per_launch, row_count);
+    plan[2] = (uint32_t)(((P + pl.batch - 1) / pl.batch) * ((row_count + pl.rows_per_launch - 1) / pl.rows_per_launch));
+    plan[3] = (uint32_t)tile_height(m->info.tile_rows, gx * slab * pl.batch);
   }
   return INFLX_OK;
 }
@@ -1402,8 +1306,8 @@ int inflx_sweep_device_stats(inflx_model* m, const double* p, size_t P, size_t n
   // `up`: the stream of the first kernel of the sweep (parameters and the initial summary are ordered before it);
   // `eval`: the stream of the kernels that accumulate (the per-row / per-column evaluation of the broadcast paths on the
   // side stream, the tile kernels on the caller's)
-  hipStream_t up = evaluates_on_side_stream(m, op, INFLX_AOS, P, N1, row_count) ? m->side : s;
-  hipStream_t eval = params_reader(m, op, INFLX_AOS, P, N1, s);
+  const SweepPlan plan = plan_sweep(m->info, op, INFLX_AOS, P, N1, row_count, INFLX_SWEEP_DEFAULT, /*alone=*/false);
+  hipStream_t up = plan.upload_stream(m, s), eval = plan.reader_stream(m, s);
   if (!m->d_stats) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_stats), 18 * sizeof(double)));
   inflx_summary init;
   for (int k = 0; k < 6; ++k) {
@@ -1416,7 +1320,7 @@ int inflx_sweep_device_stats(inflx_model* m, const double* p, size_t P, size_t n
   const double* d_params = nullptr;
   if ((rc = acquire_params(m, p, P * n_p, up, &d_params))) return rc;
   if (row_count && N1) {
-    rc = launch_grid(m, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, INFLX_AOS, s, 0, 0.0, m->d_stats);
+    rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, INFLX_AOS, s, false, 0.0, m->d_stats);
   }
   if ((rc = release_params_after(m, eval, rc))) return rc;
   HIP_TRY(hipMemcpyAsync(summary, m->d_stats, sizeof *summary, hipMemcpyDeviceToHost, eval));
@@ -1468,15 +1372,14 @@ int inflx_sweep_device_ex(inflx_model* m, int op, const double* p, size_t P, siz
   const size_t need = P * row_count * N1 * kOpBytes[op];
   if (d_out_bytes < need) return fail(INFLX_ERR_SHAPE, "output buffer has %zu bytes, the sweep writes %zu", d_out_bytes, need);
   HIP_TRY(hipSetDevice(m->device));
-  FlagScope scope(m, flags);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
   // the parameters are read by the kernel that evaluates the model: the per-row / per-column evaluation or the stage tables -- on the
   // side stream while an earlier sweep of this handle is still running (they overlap it), on the caller's stream at an idle handle
-  hipStream_t up = evaluates_on_side_stream(m, op, layout, P, N1, row_count, /*alone=*/handle_idle(m)) ? m->side : s;
+  const SweepPlan plan = plan_sweep(m->info, op, layout, P, N1, row_count, flags, /*alone=*/handle_idle(m));
   const double* d_params = nullptr;
-  if ((rc = acquire_params(m, p, P * n_p, up, &d_params))) return rc;
-  rc = launch_grid(m, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s);
-  rc = release_params_after(m, params_reader(m, op, layout, P, N1, s), rc);
+  if ((rc = acquire_params(m, p, P * n_p, plan.upload_stream(m, s), &d_params))) return rc;
+  rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s);
+  rc = release_params_after(m, plan.reader_stream(m, s), rc);
   if (rc == INFLX_OK && !m->sf_words.empty() && s != m->stream) {  // (see sf_done: the stream that finishes the sweep is the caller's)
     if (!m->sf_done) HIP_TRY(hipEventCreateWithFlags(&m->sf_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(m->sf_done, s));
@@ -1501,7 +1404,6 @@ int inflx_sweep_device_timed_ex(inflx_model* m, int op, const double* p, size_t 
   // first call validates everything and uploads the parameters
   int rc = inflx_sweep_device_ex(m, op, p, P, n_p, d_out, d_out_bytes, ss, N0, N1, row_begin, row_count, layout, stream, flags);
   if (rc) return rc;
-  FlagScope scope(m, flags);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
   if (mode == INFLX_TIME_SINGLE_CALL) {
     // what ONE call costs a caller whose handle is idle: every repetition waits until the device has nothing of this handle left,
@@ -1528,8 +1430,8 @@ int inflx_sweep_device_timed_ex(inflx_model* m, int op, const double* p, size_t 
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(m->side));
   // the repetitions are enqueued back to back: the shape of a sweep that arrives while its predecessor runs (tables on the side stream)
-  (void)evaluates_on_side_stream(m, op, layout, P, N1, row_count, /*alone=*/false);
-  const hipStream_t reader = params_reader(m, op, layout, P, N1, s);
+  const SweepPlan plan = plan_sweep(m->info, op, layout, P, N1, row_count, flags, /*alone=*/false);
+  const hipStream_t reader = plan.reader_stream(m, s);
   // dominant_only == 2: the full sweeps, with an event pair around every dominant-kernel launch (at most 64 per sweep)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;
   struct Disarm {
@@ -1555,8 +1457,8 @@ int inflx_sweep_device_timed_ex(inflx_model* m, int op, const double* p, size_t 
   }
   HIP_TRY(hipEventRecord(m->t0, s));
   for (int k = 0; k < repeats; ++k) {
-    rc = launch_grid(m, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s,
-                     dominant_only == 1 ? 2 : 0);
+    rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s,
+                     /*stores_only=*/dominant_only == 1);
     if (rc) return release_params_after(m, reader, rc);
   }
   HIP_TRY(hipEventRecord(m->t1, s));
@@ -1938,17 +1840,17 @@ int sweep_host_body(inflx_model* m, int op, const double* p, size_t P, size_t n_
       whole = false;  // (a plane subset too: the pipeline below copies the requested planes of every chunk)
     }
   }
-  // the stream of the kernels that read the parameters: decided by the P the launches below really see (the
-  // whole-result path launches all P rows at once, the chunk pipeline one parameter row at a time)
-  hipStream_t reader = evaluates_on_side_stream(m, op, layout, whole ? P : 1, N1, row_count, /*alone=*/whole) ? m->side : m->stream;
+  // planned with the P the launches below really see (the whole-result path launches all P rows at once, the chunk pipeline one
+  // parameter row at a time, back to back); both paths wait for their streams before they return, so the slot needs no release
+  const SweepPlan plan = plan_sweep(m->info, op, layout, whole ? P : 1, N1, row_count, INFLX_SWEEP_DEFAULT, /*alone=*/whole);
   const double* d_params = nullptr;
-  if ((rc = acquire_params(m, p, P * n_p, reader, &d_params))) return rc;
+  if ((rc = acquire_params(m, p, P * n_p, plan.upload_stream(m, m->stream), &d_params))) return rc;
   if (whole) {
     // One launch for everything, and as few copies as the destination allows (one when the caller's array is the slab):
     // the device buffer has the layout of the slab.  The destination pages are made resident by helper threads that run
     // ahead of the copy: the first stretch before the copy starts, the rest -- in stripes dealt round-robin, so that the
     // resident frontier advances at the aggregate rate, several times the PCIe rate -- while it is under way.
-    rc = launch_grid(m, op, d_params, P, static_cast<double*>(m->d_whole), ss, N0, N1, row_begin, row_count, layout, m->stream, 0, accuracy);
+    rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(m->d_whole), ss, N0, N1, row_begin, row_count, layout, m->stream, false, accuracy);
     if (rc) {  // kernels enqueued before the failure may still read the parameter slot
       (void)hipStreamSynchronize(m->side);
       (void)hipStreamSynchronize(m->stream);
@@ -2101,8 +2003,8 @@ int sweep_host_body(inflx_model* m, int op, const double* p, size_t P, size_t n_
       if (progress)
         for (; counted + 2 <= c; ++counted) progress->done += pieces[counted].nrows * piece_row_bytes;
     }
-    rc = launch_grid(m, op, d_params + pc.pr * n_p, 1, static_cast<double*>(m->d_chunk[b]), ss, N0, N1, row_begin + pc.r, pc.nrows, layout,
-                     m->stream, 0, accuracy);
+    rc = launch_grid(m, plan, op, d_params + pc.pr * n_p, 1, static_cast<double*>(m->d_chunk[b]), ss, N0, N1, row_begin + pc.r, pc.nrows, layout,
+                     m->stream, false, accuracy);
     if (rc) { drain(); return rc; }
     if (ready.valid()) ready.wait();  // pages of this chunk's destination are resident
     if (c + 1 < pieces.size()) ready = start_touch(pieces[c + 1]);

@@ -152,6 +152,46 @@ int main() {
       if (th < full / 2) CHECK(seg / th >= 1024 || th == 1);  // lower tiles only while they are needed to reach ~1024 workgroups
     }
   }
+  // ---- the plan of a sweep: tests/golden/sweep_plans.txt holds what the library decided per sweep -- path, batches, replicas, where
+  // the tables are evaluated, the streams of the parameter upload and of the last parameter reader -- when these decisions were
+  // still made in several places (recorded at the commit its first line names, with the geometry constants of the kernels);
+  // plan_sweep, the two stream accessors and inflx_sweep_plan_ex must decide the same, line for line
+  {
+    std::string golden = __FILE__;
+    golden = golden.substr(0, golden.find_last_of('/')) + "/golden/sweep_plans.txt";
+    FILE* fh = fopen(golden.c_str(), "r");
+    CHECK(fh != nullptr);
+    inflx_model handle;  // never opened: two distinct stream values are all the accessors look at
+    handle.side = reinterpret_cast<hipStream_t>(0x10);
+    const hipStream_t callers = reinterpret_cast<hipStream_t>(0x20);
+    InflxKernelInfo& info = handle.info;
+    info.kernel_abi = INFLX_KERNEL_ABI;
+    info.tile_cols = 256, info.rows_per_block = 4, info.row_chunk_units = 256;
+    char line[512];
+    size_t replayed = 0;
+    while (fgets(line, sizeof line, fh)) {
+      if (line[0] == '#') continue;
+      unsigned flags, want[4];
+      int op, layout, alone, one_stream, upload_on_side, reader_on_side;
+      size_t P, N1, rows;
+      CHECK(sscanf(line, "%u %u %u %u %u %d %d %u %d %zu %zu %zu -> %u %u %u %u %d %d %d", &info.out_mask, &info.n_uniform, &info.n_row, &info.n_col,
+                   &info.tile_rows, &op, &layout, &flags, &alone, &P, &N1, &rows, &want[0], &want[1], &want[2], &want[3], &one_stream, &upload_on_side,
+                   &reader_on_side) == 19);
+      const SweepPlan pl = plan_sweep(info, op, layout, P, N1, rows, flags, alone != 0);
+      CHECK(pl.path == (int)want[0] && pl.one_stream == (one_stream != 0));
+      CHECK(pl.upload_stream(&handle, callers) == (upload_on_side ? handle.side : callers));
+      CHECK(pl.reader_stream(&handle, callers) == (reader_on_side ? handle.side : callers));
+      if (pl.path != INFLX_PATH_ROWS) CHECK(pl.batch == want[1]);
+      if (pl.path == INFLX_PATH_ROW_STREAM) CHECK(pl.replicas == want[3]);
+      if (pl.path == INFLX_PATH_TILE) CHECK(pl.rows_per_launch == size_t(65535) * info.tile_rows);
+      uint32_t got[4];
+      CHECK(inflx_sweep_plan_ex(&handle, op, P, N1, rows, layout, flags, got) == INFLX_OK);
+      CHECK(got[0] == want[0] && got[1] == want[1] && got[2] == want[2] && got[3] == want[3]);
+      ++replayed;
+    }
+    fclose(fh);
+    CHECK(replayed == 4388);
+  }
   // ---- the reporter starts and stops cleanly whether or not it ever prints
   {
     Progress pr;
