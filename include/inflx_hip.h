@@ -440,11 +440,30 @@ typedef enum inflx_eom_status {
   INFLX_EOM_ENDED = 1,      /* epsilon_H reached 1 (INFLX_EOM_STOP_AT_END) */
   INFLX_EOM_NONFINITE = 2,  /* the state or the equations of motion at it are not finite */
   INFLX_EOM_REJECTED = 3,   /* 50 consecutive rejected steps */
-  INFLX_EOM_UNDERFLOW = 4   /* the step no longer moves t */
+  INFLX_EOM_UNDERFLOW = 4,  /* the step no longer moves t */
+  INFLX_EOM_TARGET = 5      /* N reached its target (inflx_solve_eom_to_efolds) */
 } inflx_eom_status;
 int inflx_solve_eom(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps,
                     int method, double max_err, double dt, unsigned flags, double* states, double* t, double* efolds, int8_t* status,
                     int64_t* last_row);
+
+/*
+ * The state of B trajectories where each has made `target[l]` e-folds: inflx_solve_eom's final-only run with one more way for a lane
+ * to stop.  A lane stops at the first accepted step whose new state has N >= its target, with INFLX_EOM_TARGET and the state where
+ * N equals the target inside that step: the cubic Hermite interpolant over the step (fourth order, as the steppers), N set to the
+ * target exactly.  A target <= 0 is reached by the initial state.  With INFLX_EOM_STOP_AT_END (the only flag) a lane whose
+ * epsilon_H reaches 1 before its target stops with INFLX_EOM_ENDED as in inflx_solve_eom.
+ *   p, P, n_p, init, B, method, max_err, dt    as for inflx_solve_eom
+ *   target     (B,): the target on N of every trajectory; a NaN is INFLX_ERR_ARG
+ *   max_steps  accepted steps a trajectory may take (INFLX_EOM_COMPLETE when they run out before the target)
+ *   states     (B, 6), t (B,), eps_h (B,): where each trajectory stopped -- for INFLX_EOM_TARGET the located state, its time and
+ *              epsilon_H at it (eps_h is NaN for every other status);  efolds (B,): N at epsilon_H = 1, meaningful for
+ *              INFLX_EOM_ENDED;  status (B,) inflx_eom_status
+ * Every output except `status` may be NULL.  Memory on the device is O(B); launches stop once no trajectory runs any more.
+ */
+int inflx_solve_eom_to_efolds(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* target,
+                              size_t max_steps, int method, double max_err, double dt, unsigned flags, double* states, double* t,
+                              double* eps_h, double* efolds, int8_t* status);
 
 #ifdef __cplusplus
 }

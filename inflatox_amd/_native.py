@@ -105,6 +105,10 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, C.POINTER(C.c_int8), C.POINTER(C.c_int64)],
     ),
+    "inflx_solve_eom_to_efolds": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, _DP, C.POINTER(C.c_int8)],
+    ),
 }
 
 
@@ -446,6 +450,29 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return states, t, efolds, status, last_row
+
+    def solve_eom_to_efolds(self, p, init, target, max_steps: int, method: int, max_err: float, dt: float, flags: int):
+        """B trajectories from ``init`` (B,4), each until its e-fold count reaches ``target`` (B,) (include/inflx_hip.h:
+        inflx_solve_eom_to_efolds).  Returns (states (B, 6), t, eps_h, efolds, status (int8)): where every trajectory stopped -- the
+        located state for status ``INFLX_EOM_TARGET``.  ``flags``: ``EOM_STOP_AT_END`` or 0."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        target = _f64(target, "target")
+        B = init.shape[0]
+        if target.shape != (B,):
+            raise InflatoxShapeError(f"target must have shape ({B},) (got {target.shape})")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        states = np.empty((B, 6))
+        t, eps_h, efolds = np.empty(B), np.empty(B), np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        _check(
+            self._lib.inflx_solve_eom_to_efolds(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, _ptr(target), int(max_steps), int(method), float(max_err), float(dt), int(flags),
+                _ptr(states), _ptr(t), _ptr(eps_h), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+            )
+        )  # fmt: skip
+        return states, t, eps_h, efolds, status
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

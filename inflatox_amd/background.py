@@ -3,7 +3,9 @@
 ``solve_eom`` is the reference's ``inflatox.background.solve_eom`` (python/inflatox/background.py) -- same signature, defaults and
 return value.  ``solve_eom_batch`` integrates many initial conditions or parameter rows at once, one GPU lane per trajectory, and
 ``efolds_map`` places initial conditions on a sweep grid and returns the number of e-folds at the end of inflation there: the
-counterpart of a consistency map from ``GeneralisedAL.complete_analysis`` over the same grid.
+counterpart of a consistency map from ``GeneralisedAL.complete_analysis`` over the same grid.  ``state_at_efolds`` returns the
+state at which a trajectory has made a given number of e-folds, and ``horizon_exit_map`` the state N_star e-folds before the end
+of inflation from every grid point: the (phi, chi, H) at which ``complete_analysis_ot`` and ``calc_V_array`` are evaluated.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -27,16 +29,20 @@ from . import _native
 from ._native import InflatoxShapeError
 from .compiler import CompilationArtifact
 
-__all__ = ["solve_eom", "solve_eom_batch", "efolds_map", "EoMSolution", "STATUS"]
+__all__ = ["solve_eom", "solve_eom_batch", "efolds_map", "state_at_efolds", "horizon_exit_map", "EoMSolution", "EfoldsState", "STATUS"]
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
-COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW = 0, 1, 2, 3, 4
+COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
+#: ``horizon_exit_map`` only (no kernel status): inflation ended, but after fewer than N_star e-folds
+ENDED_SHORT = 6
 STATUS = {
     COMPLETE: "every requested step was taken",
     ENDED: "epsilon_H reached 1 (stop_at_end)",
     NONFINITE: "the state or the equations of motion at it are not finite",
     REJECTED: "50 consecutive rejected steps",
     UNDERFLOW: "the step size no longer moves t",
+    TARGET: "N reached its target (state_at_efolds, horizon_exit_map)",
+    ENDED_SHORT: "epsilon_H reached 1 after fewer than N_star e-folds (horizon_exit_map)",
 }
 _METHODS = {"rk4": _native.EOM_RK4, "rkf": _native.EOM_RKF}
 
@@ -52,6 +58,19 @@ class EoMSolution(NamedTuple):
     status: np.ndarray
     last_row: np.ndarray
     N_end: np.ndarray
+
+
+class EfoldsState(NamedTuple):
+    """What :func:`state_at_efolds` returns.  ``state`` (B, 5): phi^0, phi^1, chi^0, chi^1, H where N = ``N_target``; ``t``, ``N``
+    and ``eps_H`` (B,): cosmic time, e-folds (the target) and epsilon_H there -- all NaN unless ``status`` (B,) int8 is ``TARGET``;
+    ``N_end`` (B,): N at epsilon_H = 1 of a trajectory that ENDED before its target (``stop_at_end``), NaN otherwise."""
+
+    state: np.ndarray
+    t: np.ndarray
+    N: np.ndarray
+    eps_H: np.ndarray
+    N_end: np.ndarray
+    status: np.ndarray
 
 
 def _dylib(artifact: CompilationArtifact) -> _native.InflatoxDevLib:
@@ -188,3 +207,71 @@ def efolds_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int
     n_end = np.where(status == ENDED, n_end, np.nan).reshape(N0, N1)
     status = status.reshape(N0, N1)
     return (n_end, status) if return_status else n_end
+
+
+def state_at_efolds(artifact: CompilationArtifact, pars, fields_init, derivatives_init, N_target, max_steps: int = 100_000, max_err: float = 1e-8,
+                    solver: str = "rkf", *, dt: float | None = None, stop_at_end: bool = True) -> EfoldsState:  # fmt: skip
+    """The state of B trajectories where each has made ``N_target`` e-folds (a scalar, or (B,): one target per trajectory), without
+    storing rows: memory is O(B).  ``fields_init``, ``derivatives_init``, ``pars``, ``solver``, ``max_err`` and ``dt`` as for
+    ``solve_eom_batch``.  A trajectory stops at the first accepted step whose new state has N >= its target (status ``TARGET``) and
+    the state is located inside that step: the cubic Hermite interpolant over the step from the states and right-hand sides at its
+    two ends -- fourth order, like the steppers --, solved for N = target by a bracketed Newton iteration, N set to the target
+    exactly and epsilon_H evaluated at the located state.  A target <= 0 is reached by the initial state.  With ``stop_at_end`` a
+    trajectory whose epsilon_H reaches 1 before its target stops there (``ENDED``, ``N_end`` as in ``efolds_map``); one that takes
+    ``max_steps`` accepted steps without reaching its target is ``COMPLETE``.  Bad arguments raise before anything runs on the
+    device."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    B = x.shape[0]
+    target = np.asarray(N_target, dtype=np.float64)
+    if target.ndim == 0:
+        target = np.full(B, float(target))
+    if target.shape != (B,):
+        raise InflatoxShapeError(f"N_target must be a scalar or have shape ({B},) (got {target.shape})")
+    if not np.isfinite(target).all():
+        raise ValueError("N_target must be finite")
+    p = _pars(artifact, pars, B)
+    init = np.concatenate([x, v], axis=1)
+    flags = _native.EOM_STOP_AT_END if stop_at_end else 0
+    states, t, eps, n_end, status = _dylib(artifact).solve_eom_to_efolds(p, init, np.ascontiguousarray(target), max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
+    hit = status == TARGET
+    states = np.where(hit[:, None], states, np.nan)
+    return EfoldsState(states[:, :5], np.where(hit, t, np.nan), states[:, 5], np.where(hit, eps, np.nan), np.where(status == ENDED, n_end, np.nan), status)
+
+
+def horizon_exit_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, derivatives_init=(0.0, 0.0),
+                     max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """The state ``N_star`` e-folds before the end of inflation -- the horizon exit of the pivot scale -- from every point of the
+    (N0, N1) grid of ``efolds_map`` (same arguments): ``(state, N_end)`` with ``state`` (N0, N1, 5) = phi^0, phi^1, chi^0, chi^1, H
+    at N = N_end - N_star and ``N_end`` (N0, N1) exactly ``efolds_map``'s result.  Two passes, each of O(N0 * N1) memory: the first
+    is ``efolds_map``'s run and finds N_end; the second, ``state_at_efolds`` with the target N_end - N_star, runs only the points
+    that ended with N_end >= N_star.  It has to be a second pass because N_end is not known before the trajectory has ended, and
+    it retraces the first exactly because the integrator is deterministic.  ``state`` is NaN everywhere else;
+    ``return_status=True`` adds the (N0, N1) int8 status map: ``TARGET`` where the state was found, ``ENDED_SHORT`` where
+    inflation ended after fewer than ``N_star`` e-folds, and the first pass's status (``COMPLETE``: never ended, or a failure)
+    otherwise.  The state carries the error of N_end (see ``efolds_map``) times |dphi/dN|."""
+    N_star = float(N_star)
+    if not (math.isfinite(N_star) and N_star >= 0.0):
+        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    n_end, status = efolds_map(artifact, pars, start_stop, N0, N1, derivatives_init, max_steps, max_err, solver, return_status=True)
+    N0, N1 = n_end.shape
+    status = status.copy().reshape(-1)
+    flat_end = n_end.reshape(-1)
+    ended = status == ENDED
+    status[ended] = ENDED_SHORT
+    state = np.full((N0 * N1, 5), np.nan)
+    with np.errstate(invalid="ignore"):
+        run = np.flatnonzero(ended & (flat_end >= N_star))
+    if run.size:
+        x0, x1 = grid_points(start_stop, N0, N1)
+        x = np.stack([np.repeat(x0, N1), np.tile(x1, N0)], axis=1)[run]
+        v = np.broadcast_to(np.asarray(derivatives_init, dtype=np.float64).reshape(2), x.shape)
+        got = state_at_efolds(artifact, pars, x, v, flat_end[run] - N_star, max_steps, max_err, solver)
+        state[run] = got.state
+        status[run] = got.status
+    state = state.reshape(N0, N1, 5)
+    status = status.reshape(N0, N1)
+    return (state, n_end, status) if return_status else (state, n_end)

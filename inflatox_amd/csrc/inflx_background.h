@@ -26,12 +26,14 @@ enum InflxBgStatus {
   INFLX_BG_NONFINITE = 2,  // the state or the equations of motion at it are not finite
   INFLX_BG_REJECTED = 3,   // INFLX_BG_MAX_REJECTIONS consecutive rejected steps
   INFLX_BG_UNDERFLOW = 4,  // t + dt == t
+  INFLX_BG_TARGET = 5,     // N reached its target (inflx_bg_step_target); the lane holds the state located there
 };
 
 enum InflxBgMethod { INFLX_BG_RK4 = 0, INFLX_BG_RKF = 1 };
 
 #define INFLX_BG_MAX_REJECTIONS 50
 #define INFLX_BG_FIRST_DT 1e-10
+#define INFLX_BG_MAX_LOCATE 64  // iterations of the root search for theta inside a step (inflx_bg_locate)
 
 // One lane: the state, the right-hand side at it (k1 of the next step, and the kinetic term G_ab chi^a chi^b), t and dt.
 struct InflxBgLane {
@@ -179,9 +181,11 @@ INFLX_FN double inflx_bg_factor(double max_err, double err) {
 }
 
 // One accepted step (fixed_dt > 0: of that size, without error control).  Returns INFLX_BG_RUNNING, or the status that stops the
-// lane; `n_end` receives N at epsilon_H = 1 when stop_at_end ends it (linear in epsilon_H across the step).
+// lane; `n_end` receives N at epsilon_H = 1 when stop_at_end ends it (linear in epsilon_H across the step); `h_taken` the size of
+// the accepted step (the lane's dt is already the next step's).
 template <int METHOD>
-INFLX_FN int inflx_bg_step(InflxBgLane& s, const double* __restrict__ p, double max_err, double fixed_dt, bool stop_at_end, double& n_end) {
+INFLX_FN int inflx_bg_step_taken(InflxBgLane& s, const double* __restrict__ p, double max_err, double fixed_dt, bool stop_at_end, double& n_end,
+                                 double& h_taken) {
   const bool adaptive = !(fixed_dt > 0.0);
   const double eps0 = inflx_bg_epsilon(s), n0 = s.y[5];
   double y1[6];
@@ -192,10 +196,12 @@ INFLX_FN int inflx_bg_step(InflxBgLane& s, const double* __restrict__ p, double 
     const bool finite = inflx_bg_finite6(y1) && isfinite(err);
     if (!adaptive) {
       if (!finite) return INFLX_BG_NONFINITE;
+      h_taken = s.dt;
       s.t += s.dt;
       break;
     }
     if (finite && err <= 1.1 * max_err) {
+      h_taken = s.dt;
       s.t += s.dt;
       s.dt *= inflx_bg_factor(max_err, err);
       break;
@@ -214,4 +220,102 @@ INFLX_FN int inflx_bg_step(InflxBgLane& s, const double* __restrict__ p, double 
     }
   }
   return INFLX_BG_RUNNING;
+}
+
+template <int METHOD>
+INFLX_FN int inflx_bg_step(InflxBgLane& s, const double* __restrict__ p, double max_err, double fixed_dt, bool stop_at_end, double& n_end) {
+  double h_taken = 0.0;
+  return inflx_bg_step_taken<METHOD>(s, p, max_err, fixed_dt, stop_at_end, n_end, h_taken);
+}
+
+// ---- a target on N: the state where a trajectory has made n_target e-folds ------------------------------------------------------
+// Dense output over an accepted step of size h from (y0, f0 = f(y0)) to (y1, f1 = f(y1)): the cubic Hermite interpolant
+//     y(theta) = h00 y0 + h10 h f0 + h01 y1 + h11 h f1,   theta in [0, 1],
+// which is within O(h^4) of the solution, the order of both steppers' states.
+INFLX_FN double inflx_bg_hermite(double y0, double f0, double y1, double f1, double h, double th) {
+  const double u = 1.0 - th;
+  const double h00 = (1.0 + 2.0 * th) * u * u, h10 = th * u * u, h01 = th * th * (3.0 - 2.0 * th), h11 = -(th * th) * u;
+  return h00 * y0 + h10 * (h * f0) + h01 * y1 + h11 * (h * f1);
+}
+
+// d/dtheta of the interpolant
+INFLX_FN double inflx_bg_hermite_slope(double y0, double f0, double y1, double f1, double h, double th) {
+  const double u = 1.0 - th;
+  const double d00 = -6.0 * th * u, d10 = u * (1.0 - 3.0 * th), d11 = th * (3.0 * th - 2.0);
+  return d00 * y0 + d10 * (h * f0) - d00 * y1 + d11 * (h * f1);
+}
+
+// theta in [0, 1] with N(theta) = n_target, for N(0) < n_target <= N(1): Newton's iteration on the interpolant of N, kept inside a
+// bracket [lo, hi] with N(lo) < n_target <= N(hi) that every iterate tightens; an iterate that leaves the bracket (N is monotone
+// across the step only where H > 0) is replaced by the bracket's midpoint.  At most INFLX_BG_MAX_LOCATE iterations.
+INFLX_FN double inflx_bg_locate(double n0, double h0, double n1, double h1, double h, double n_target) {
+  double lo = 0.0, hi = 1.0;
+  double th = (n_target - n0) / (n1 - n0);
+  if (!(th > 0.0)) th = 0.0;
+  if (th > 1.0) th = 1.0;
+  for (int it = 0; it < INFLX_BG_MAX_LOCATE; ++it) {
+    const double g = inflx_bg_hermite(n0, h0, n1, h1, h, th) - n_target;
+    if (g == 0.0) break;
+    if (g < 0.0)
+      lo = th;
+    else
+      hi = th;
+    double next = th - g / inflx_bg_hermite_slope(n0, h0, n1, h1, h, th);
+    if (!(next > lo && next < hi)) next = 0.5 * (lo + hi);
+    const double moved = fabs(next - th);
+    th = next;
+    if (moved <= 1e-15 || hi - lo <= 1e-15) break;
+  }
+  return th;
+}
+
+// the located state of a lane that reached its target: y[0..5] (N = the target exactly), t, and epsilon_H there
+struct InflxBgLocated {
+  double y[6];
+  double t;
+  double eps;
+};
+
+// epsilon_H at the located state (one evaluation of the model); false: the state or epsilon_H is not finite
+INFLX_FN bool inflx_bg_located_epsilon(InflxBgLocated& loc, const double* __restrict__ p) {
+  double o[4];
+  inflx_eom_point(loc.y[0], loc.y[1], loc.y[2], loc.y[3], p, o);
+  loc.eps = 0.5 * o[3] / (loc.y[4] * loc.y[4]);
+  return inflx_bg_finite6(loc.y) && isfinite(loc.t) && isfinite(loc.eps);
+}
+
+// inflx_bg_init for a lane with a target: a target <= 0 is reached by the initial state (INFLX_BG_TARGET, t = 0) -- unless that
+// state is already past the end of inflation with stop_at_end, which ends the lane as in inflx_bg_init.
+INFLX_FN int inflx_bg_init_target(InflxBgLane& s, const double* init, const double* __restrict__ p, double dt0, bool stop_at_end, double n_target,
+                                  double& n_end, InflxBgLocated& loc) {
+  const int st = inflx_bg_init(s, init, p, dt0, stop_at_end, n_end);
+  if (st != INFLX_BG_RUNNING || !(n_target <= 0.0)) return st;
+  for (int c = 0; c < 6; ++c) loc.y[c] = s.y[c];
+  loc.t = s.t;
+  loc.eps = inflx_bg_epsilon(s);
+  return INFLX_BG_TARGET;
+}
+
+// One accepted step of a lane with a target: inflx_bg_step, and when the new state has N >= n_target the lane stops with
+// INFLX_BG_TARGET and `loc` = the state where N = n_target inside that step: the Hermite interpolant at the theta of
+// inflx_bg_locate, N set to the target, t = t0 + theta h, epsilon_H from the model at that state (not finite: INFLX_BG_NONFINITE).
+// A step that also ends inflation (stop_at_end) ends the lane instead when epsilon_H = 1 comes first, n_end < n_target.
+template <int METHOD>
+INFLX_FN int inflx_bg_step_target(InflxBgLane& s, const double* __restrict__ p, double max_err, double fixed_dt, bool stop_at_end, double n_target,
+                                  double& n_end, InflxBgLocated& loc) {
+  double y0[6], f0[6], h = 0.0;
+  for (int c = 0; c < 6; ++c) {
+    y0[c] = s.y[c];
+    f0[c] = s.f[c];
+  }
+  const double t0 = s.t;
+  const int st = inflx_bg_step_taken<METHOD>(s, p, max_err, fixed_dt, stop_at_end, n_end, h);
+  if (st != INFLX_BG_RUNNING && st != INFLX_BG_ENDED) return st;
+  if (!(s.y[5] >= n_target)) return st;
+  if (st == INFLX_BG_ENDED && n_end < n_target) return st;
+  const double th = inflx_bg_locate(y0[5], f0[5], s.y[5], s.f[5], h, n_target);
+  for (int c = 0; c < 5; ++c) loc.y[c] = inflx_bg_hermite(y0[c], f0[c], s.y[c], s.f[c], h, th);
+  loc.y[5] = n_target;
+  loc.t = t0 + th * h;
+  return inflx_bg_located_epsilon(loc, p) ? INFLX_BG_TARGET : INFLX_BG_NONFINITE;
 }

@@ -5,7 +5,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#define INFLX_BG_ABI_VERSION 2
+// (overridable with -DINFLX_BG_ABI_VERSION=<n> so that a test can build an object of another layout version and see it refused)
+#ifndef INFLX_BG_ABI_VERSION
+#define INFLX_BG_ABI_VERSION 3
+#endif
 // the artefact ABI major a background object reports by default: the core object's (csrc/inflx_sweep_kernels.hip, overridable there
 // and here with -DINFLX_ABI_VERSION_MAJOR, which the background object is built with whenever the core object is)
 #define INFLX_BG_DEFAULT_ABI_MAJOR 5
@@ -19,12 +22,16 @@ enum InflxBgCarry {
   INFLX_BG_CARRY_STATUS = 9,
   INFLX_BG_CARRY_LAST_ROW = 10, // index of the last row that holds a state
   INFLX_BG_CARRY_PENDING = 11,  // 1: the lane ended inside a row that has not been written yet (that row holds the end state)
-  INFLX_BG_CARRY_PLANES = 12,
+  INFLX_BG_CARRY_ROW_PLANES = 12,  // the planes inflx_solve_eom reads back
+  INFLX_BG_CARRY_EPS = 12,      // epsilon_H at the located state of a lane that reached its target on N (NaN otherwise)
+  INFLX_BG_CARRY_PLANES = 13,
 };
 
 // Argument block of inflx_bg_init and inflx_bg_advance_*.  A launch of the advance kernels processes the accepted-step indices
 // [step_begin, step_begin + steps) of every lane -- the same indices for all lanes, whether they still run or not --, and row r is
-// complete after step index r*substeps - 1; it goes to slot r - row_base of `rows`.
+// complete after step index r*substeps - 1; it goes to slot r - row_base of `rows`.  The *_target kernels (final-only, substeps = 1)
+// stop a lane at its target on N as well: the lane's carry then holds the located state (planes Y, T, EPS).  They skip a lane that
+// has stopped, and add the number of lanes still running after the launch to *running.
 struct InflxBgArgs {
   const double* p;       // parameter rows of lane 0 of this launch
   uint64_t p_stride;     // doubles between the parameter rows of two lanes (0: one row for all)
@@ -40,9 +47,12 @@ struct InflxBgArgs {
   uint32_t reserved;
   double max_err;
   double fixed_dt;       // > 0: fixed step
+  const double* target;  // (n,): the target on N of every lane (init and *_target kernels) -- or NULL
+  uint32_t* running;     // *_target kernels: one word, += the lanes still running when the launch ends
 };
-static_assert(sizeof(InflxBgArgs) == 96, "InflxBgArgs layout");
-static_assert(offsetof(InflxBgArgs, step_begin) == 48 && offsetof(InflxBgArgs, steps) == 64 && offsetof(InflxBgArgs, max_err) == 80,
+static_assert(sizeof(InflxBgArgs) == 112, "InflxBgArgs layout");
+static_assert(offsetof(InflxBgArgs, step_begin) == 48 && offsetof(InflxBgArgs, steps) == 64 && offsetof(InflxBgArgs, max_err) == 80 &&
+                  offsetof(InflxBgArgs, target) == 96 && offsetof(InflxBgArgs, running) == 104,
               "InflxBgArgs layout");
 
 // bound of one launch: accepted steps per lane (each of at most 50 trials)

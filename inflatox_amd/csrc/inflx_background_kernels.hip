@@ -9,7 +9,9 @@
 // every lane by at most INFLX_BG_STEPS_PER_LAUNCH accepted steps, whatever the number of steps per row; between launches the state
 // lives in `carry`, planes [INFLX_BG_CARRY_PLANES][n] (lane fastest, csrc/inflx_background_abi.h).
 // Rows go to `rows`, planes [row][7][n]: y[0..5], t -- lane fastest, so that a wavefront's store of one component is 512 contiguous
-// bytes.  STORE_ROWS = false is the final-only mode (e-fold maps): nothing but the carry is written.
+// bytes.  STORE_ROWS = false is the final-only mode (e-fold maps): nothing but the carry is written.  TARGET = true (final-only)
+// adds a per-lane target on N: a lane stops at the state where N = target, located inside the accepted step that passes it
+// (inflx_bg_step_target), and that state -- with epsilon_H there -- is what its carry holds.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -62,9 +64,14 @@ extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_init(const Inf
   for (int c = 0; c < 4; ++c) init[c] = a.init[lane * 4u + c];
   InflxBgLane s;
   double n_end = __builtin_nan("");
-  const int st = inflx_bg_init(s, init, p, a.fixed_dt > 0.0 ? a.fixed_dt : INFLX_BG_FIRST_DT, (a.flags & 1u) != 0, n_end);
+  const double dt0 = a.fixed_dt > 0.0 ? a.fixed_dt : INFLX_BG_FIRST_DT;
+  InflxBgLocated loc;
+  loc.eps = __builtin_nan("");
+  const int st = a.target ? inflx_bg_init_target(s, init, p, dt0, (a.flags & 1u) != 0, a.target[lane], n_end, loc)
+                          : inflx_bg_init(s, init, p, dt0, (a.flags & 1u) != 0, n_end);
   double* cy = a.carry + lane;
   for (int c = 0; c < 6; ++c) cy[(uint64_t)(INFLX_BG_CARRY_Y + c) * a.n] = s.y[c];
+  cy[(uint64_t)INFLX_BG_CARRY_EPS * a.n] = loc.eps;
   cy[(uint64_t)INFLX_BG_CARRY_T * a.n] = s.t;
   cy[(uint64_t)INFLX_BG_CARRY_DT * a.n] = s.dt;
   cy[(uint64_t)INFLX_BG_CARRY_NEND * a.n] = n_end;
@@ -74,16 +81,53 @@ extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_init(const Inf
   if (a.rows) store_row(a.rows, a.n, 0, lane, s.y, s.t, true);  // row 0 (slot 0) is the initial state
 }
 
+// A running lane with a target on N: at most a.steps accepted steps; true while it still runs.  A lane that stops keeps in its
+// carry the state it stopped at -- the located state and epsilon_H there for INFLX_BG_TARGET.
+template <int METHOD>
+__device__ __forceinline__ bool advance_to_target(const InflxBgArgs& a, uint64_t lane, const double* p, double* cy) {
+  InflxBgLane s;
+  for (int c = 0; c < 6; ++c) s.y[c] = cy[(uint64_t)(INFLX_BG_CARRY_Y + c) * a.n];
+  s.t = cy[(uint64_t)INFLX_BG_CARRY_T * a.n];
+  s.dt = cy[(uint64_t)INFLX_BG_CARRY_DT * a.n];
+  double n_end = cy[(uint64_t)INFLX_BG_CARRY_NEND * a.n];
+  const double target = a.target[lane];
+  const bool stop_at_end = (a.flags & 1u) != 0;
+  inflx_bg_resume(s, p);
+  InflxBgLocated loc;
+  int status = INFLX_BG_RUNNING;
+  for (uint32_t i = 0; i < a.steps && status == INFLX_BG_RUNNING; ++i)
+    status = inflx_bg_step_target<METHOD>(s, p, a.max_err, a.fixed_dt, stop_at_end, target, n_end, loc);
+  const bool located = status == INFLX_BG_TARGET;
+  for (int c = 0; c < 6; ++c) cy[(uint64_t)(INFLX_BG_CARRY_Y + c) * a.n] = located ? loc.y[c] : s.y[c];
+  cy[(uint64_t)INFLX_BG_CARRY_T * a.n] = located ? loc.t : s.t;
+  cy[(uint64_t)INFLX_BG_CARRY_DT * a.n] = s.dt;
+  cy[(uint64_t)INFLX_BG_CARRY_NEND * a.n] = n_end;
+  cy[(uint64_t)INFLX_BG_CARRY_STATUS * a.n] = (double)status;
+  if (located) cy[(uint64_t)INFLX_BG_CARRY_EPS * a.n] = loc.eps;
+  return status == INFLX_BG_RUNNING;
+}
+
 // The accepted-step indices [step_begin, step_begin + steps) of one lane.  A running lane takes one accepted step per index; at
 // the end of every row (index r*substeps - 1) row r is written: the state, or NaN once the lane has stopped -- except the row in
 // which a lane ends at epsilon_H = 1, which holds the end state.  A row may span launches: nothing but the step index says where
 // in a row a launch starts, and that index is the same for every lane.
-template <int METHOD, bool STORE_ROWS>
+// TARGET: a lane that has stopped is left as it is, and every wavefront adds its lanes that still run to *a.running (the lanes of
+// a wavefront are consecutive, so its lane 0 is inside the batch whenever any of its lanes is).
+template <int METHOD, bool STORE_ROWS, bool TARGET>
 __device__ __forceinline__ void advance(const InflxBgArgs& a) {
+  static_assert(!(TARGET && STORE_ROWS), "a target on N is a final-only mode");
   const uint64_t lane = (uint64_t)blockIdx.x * kBgThreads + threadIdx.x;
   if (lane >= a.n) return;
   const double* p = a.p + lane * a.p_stride;
   double* cy = a.carry + lane;
+  if constexpr (TARGET) {
+    const bool was_running = (int)cy[(uint64_t)INFLX_BG_CARRY_STATUS * a.n] == INFLX_BG_RUNNING;
+    bool runs_on = false;
+    if (was_running) runs_on = advance_to_target<METHOD>(a, lane, p, cy);
+    const unsigned long long mask = __ballot(runs_on);
+    if ((threadIdx.x & 63u) == 0u && mask != 0ull) atomicAdd(a.running, (uint32_t)__popcll(mask));
+    return;
+  }
   InflxBgLane s;
   for (int c = 0; c < 6; ++c) s.y[c] = cy[(uint64_t)(INFLX_BG_CARRY_Y + c) * a.n];
   s.t = cy[(uint64_t)INFLX_BG_CARRY_T * a.n];
@@ -120,9 +164,11 @@ __device__ __forceinline__ void advance(const InflxBgArgs& a) {
   cy[(uint64_t)INFLX_BG_CARRY_PENDING * a.n] = pending ? 1.0 : 0.0;
 }
 
-#define INFLX_BG_KERNEL(name, METHOD, STORE) \
-  extern "C" __global__ __launch_bounds__(kBgThreads) void name(const InflxBgArgs a) { advance<METHOD, STORE>(a); }
-INFLX_BG_KERNEL(inflx_bg_advance_rk4_rows, INFLX_BG_RK4, true)
-INFLX_BG_KERNEL(inflx_bg_advance_rk4_final, INFLX_BG_RK4, false)
-INFLX_BG_KERNEL(inflx_bg_advance_rkf_rows, INFLX_BG_RKF, true)
-INFLX_BG_KERNEL(inflx_bg_advance_rkf_final, INFLX_BG_RKF, false)
+#define INFLX_BG_KERNEL(name, METHOD, STORE, TARGET) \
+  extern "C" __global__ __launch_bounds__(kBgThreads) void name(const InflxBgArgs a) { advance<METHOD, STORE, TARGET>(a); }
+INFLX_BG_KERNEL(inflx_bg_advance_rk4_rows, INFLX_BG_RK4, true, false)
+INFLX_BG_KERNEL(inflx_bg_advance_rk4_final, INFLX_BG_RK4, false, false)
+INFLX_BG_KERNEL(inflx_bg_advance_rkf_rows, INFLX_BG_RKF, true, false)
+INFLX_BG_KERNEL(inflx_bg_advance_rkf_final, INFLX_BG_RKF, false, false)
+INFLX_BG_KERNEL(inflx_bg_advance_rk4_target, INFLX_BG_RK4, false, true)
+INFLX_BG_KERNEL(inflx_bg_advance_rkf_target, INFLX_BG_RKF, false, true)

@@ -418,6 +418,7 @@ struct inflx_model {
   hipModule_t bg_module = nullptr;
   hipFunction_t bg_init = nullptr;
   hipFunction_t bg_advance[2][2] = {};  // [method][store rows]
+  hipFunction_t bg_target[2] = {};      // [method]: final-only with a target on N (inflx_solve_eom_to_efolds)
 };
 
 namespace {
@@ -2776,13 +2777,17 @@ int need_background(inflx_model* m) {
     return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another ABI (tag \"%s\", expected \"%s\")",
                      path.c_str(), m->path.c_str(), tag, m->tag.c_str()));
   const char* names[2][2] = {{"inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows"}, {"inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows"}};
-  hipFunction_t init = nullptr, adv[2][2] = {};
+  const char* target_names[2] = {"inflx_bg_advance_rk4_target", "inflx_bg_advance_rkf_target"};
+  hipFunction_t init = nullptr, adv[2][2] = {}, tgt[2] = {};
   if (hipModuleGetFunction(&init, module, "inflx_bg_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_bg_init", path.c_str()));
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b)
       if (hipModuleGetFunction(&adv[a][b], module, names[a][b]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a][b]));
+  for (int a = 0; a < 2; ++a)
+    if (hipModuleGetFunction(&tgt[a], module, target_names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), target_names[a]));
   m->bg_module = module;
   m->bg_init = init;
+  for (int a = 0; a < 2; ++a) m->bg_target[a] = tgt[a];
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b) m->bg_advance[a][b] = adv[a][b];
   note_sf_word(m, module);
@@ -2791,10 +2796,12 @@ int need_background(inflx_model* m) {
 
 // device buffers of one call, released on every way out
 struct BgBuffers {
-  double *p = nullptr, *init = nullptr, *carry = nullptr, *rows = nullptr;
+  double *p = nullptr, *init = nullptr, *carry = nullptr, *rows = nullptr, *target = nullptr;
+  uint32_t* running = nullptr;
   ~BgBuffers() {
-    for (double* d : {p, init, carry, rows})
+    for (double* d : {p, init, carry, rows, target})
       if (d) (void)hipFree(d);
+    if (running) (void)hipFree(running);
   }
 };
 
@@ -2836,7 +2843,7 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
   if (store) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.rows), cap_rows * 7 * nc_max * sizeof(double)));
-  std::vector<double> host_rows(store ? cap_rows * 7 * nc_max : 0), host_carry(nc_max * INFLX_BG_CARRY_PLANES);
+  std::vector<double> host_rows(store ? cap_rows * 7 * nc_max : 0), host_carry(nc_max * INFLX_BG_CARRY_ROW_PLANES);
   hipFunction_t advance = m->bg_advance[method == INFLX_EOM_RKF ? 1 : 0][store ? 1 : 0];
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
@@ -2898,7 +2905,7 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
       }
     }
     if (store && (rc = drain())) return rc;  // (rows == 1: the initial state only)
-    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_ROW_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
@@ -2910,6 +2917,89 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
           for (int c = 0; c < 6; ++c) states[(c0 + l) * 6 + c] = hc[(size_t)(INFLX_BG_CARRY_Y + c) * n + l];
         if (t) t[c0 + l] = hc[INFLX_BG_CARRY_T * n + l];
       }
+    }
+  }
+  return sf_verdict(m);
+}
+
+int inflx_solve_eom_to_efolds(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* target, size_t max_steps,
+                              int method, double max_err, double dt, unsigned flags, double* states, double* t, double* eps_h, double* efolds,
+                              int8_t* status) {
+  INFLX_SERIALISE(m);
+  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the background solver requires a 2-field model (model has %u fields)", m->dim);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
+  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
+  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
+  if (flags & ~(unsigned)INFLX_EOM_STOP_AT_END) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
+  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
+  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
+  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  if (!target) return fail(INFLX_ERR_ARG, "target array is NULL");
+  for (size_t l = 0; l < B; ++l)
+    if (std::isnan(target[l])) return fail(INFLX_ERR_ARG, "target %zu is NaN", l);
+  HIP_TRY(hipSetDevice(m->device));
+  int rc = need_background(m);
+  if (rc) return rc;
+  hipStream_t s = m->stream;
+  const size_t nc_max = std::min(B, kBgMaxLanes);
+  BgBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.target), nc_max * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  std::vector<double> host_carry(nc_max * INFLX_BG_CARRY_PLANES);
+  hipFunction_t advance = m->bg_target[method == INFLX_EOM_RKF ? 1 : 0];
+
+  for (size_t c0 = 0; c0 < B; c0 += nc_max) {
+    const size_t n = std::min(nc_max, B - c0);
+    InflxBgArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = buf.init;
+    a.carry = buf.carry;
+    a.n = n;
+    a.substeps = 1;
+    a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    a.target = buf.target;
+    a.running = buf.running;
+    void* params[] = {&a};
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(buf.target, target + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipModuleLaunchKernel(m->bg_init, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    // launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
+    for (uint64_t step = 0; step < (uint64_t)max_steps;) {
+      const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
+      a.step_begin = step;
+      a.steps = (uint32_t)k;
+      uint32_t running = 0;
+      HIP_TRY(hipMemsetAsync(buf.running, 0, sizeof(uint32_t), s));
+      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+      HIP_TRY(hipMemcpyAsync(&running, buf.running, sizeof running, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      step += k;
+      if (running == 0) break;
+    }
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double* hc = host_carry.data();
+    for (size_t l = 0; l < n; ++l) {
+      status[c0 + l] = (int8_t)hc[INFLX_BG_CARRY_STATUS * n + l];
+      if (efolds) efolds[c0 + l] = hc[INFLX_BG_CARRY_NEND * n + l];
+      if (eps_h) eps_h[c0 + l] = hc[INFLX_BG_CARRY_EPS * n + l];
+      if (states)
+        for (int c = 0; c < 6; ++c) states[(c0 + l) * 6 + c] = hc[(size_t)(INFLX_BG_CARRY_Y + c) * n + l];
+      if (t) t[c0 + l] = hc[INFLX_BG_CARRY_T * n + l];
     }
   }
   return sf_verdict(m);

@@ -7,7 +7,9 @@ rows stored or copied: kernels plus one carry copy) for B in {2^14, 2^17, 2^20},
 
     rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/background_probe.py --quick
 
-(kernels ``inflx_bg_advance_*``).  Run from the repository root on the GPU box.
+(kernels ``inflx_bg_advance_*``).  ``--horizon-exit`` times nothing but ``horizon_exit_map`` beside ``efolds_map`` on the same
+1024^2 hyperbolic grid (best of three calls each, after a warm-up) and writes ``profiles/background_horizon_exit.json``.  Run from
+the repository root on the GPU box.
 """
 
 import argparse
@@ -55,11 +57,41 @@ def batch(name, B, rows=256, substeps=4, seed=0):
                      status_counts={int(k): int(c) for k, c in zip(*np.unique(fstatus, return_counts=True))})  # fmt: skip
 
 
+def horizon_exit(n=1024, n_star=1.0, repeats=3):
+    spec, art = workloads.artifact_for("hyperbolic")
+    ss = [[1.0, 5.0], [-1.0, 1.0]]
+    background.horizon_exit_map(art, spec.args, ss, 32, 32, N_star=n_star)  # build / load / warm up
+
+    def best(fn):
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            out = fn()
+            times.append(time.perf_counter() - t0)
+        return min(times), out
+
+    t_map, n_end = best(lambda: background.efolds_map(art, spec.args, ss, n, n))
+    t_exit, (state, n_end2, status) = best(lambda: background.horizon_exit_map(art, spec.args, ss, n, n, N_star=n_star, return_status=True))
+    assert np.array_equal(n_end, n_end2, equal_nan=True)
+    rec = dict(model="hyperbolic", code_object=art._build[2], grid=[n, n], start_stop=ss, N_star=n_star, repeats=repeats,
+               efolds_map_s=t_map, horizon_exit_map_s=t_exit, ratio=t_exit / t_map, ended=int(np.isfinite(n_end).sum()),
+               exit_states=int(np.isfinite(state).all(axis=2).sum()),
+               status_counts={int(k): int(c) for k, c in zip(*np.unique(status, return_counts=True))},
+               command="python scripts/background_probe.py --horizon-exit")  # fmt: skip
+    print(json.dumps(rec), flush=True)
+    with open(os.path.join(ROOT, "profiles", "background_horizon_exit.json"), "w") as fh:
+        json.dump(rec, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--horizon-exit", action="store_true", help="time horizon_exit_map beside efolds_map at 1024^2 on hyperbolic, nothing else")
     ap.add_argument("--quick", action="store_true", help="B = 2^14 only (for a profiler run)")
     ap.add_argument("--max-log2-lanes", type=int, default=20)
     args = ap.parse_args()
+    if args.horizon_exit:
+        horizon_exit()
+        return
     sizes = [14] if args.quick else [k for k in (14, 17, 20) if k <= args.max_log2_lanes]
     for name in ("hyperbolic", "egno"):
         rec = {"model": name, "runs": []}
