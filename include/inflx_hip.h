@@ -433,7 +433,8 @@ typedef enum inflx_eom_method {
 } inflx_eom_method;
 typedef enum inflx_eom_flags {
   INFLX_EOM_STOP_AT_END = 1,
-  INFLX_EOM_FINAL_ONLY = 2
+  INFLX_EOM_FINAL_ONLY = 2,
+  INFLX_EOM_SAMPLE_T = 4    /* inflx_solve_eom_sampled: the samples are times, not e-fold counts */
 } inflx_eom_flags;
 typedef enum inflx_eom_status {
   INFLX_EOM_COMPLETE = 0,   /* every requested step was taken */
@@ -441,7 +442,7 @@ typedef enum inflx_eom_status {
   INFLX_EOM_NONFINITE = 2,  /* the state or the equations of motion at it are not finite */
   INFLX_EOM_REJECTED = 3,   /* 50 consecutive rejected steps */
   INFLX_EOM_UNDERFLOW = 4,  /* the step no longer moves t */
-  INFLX_EOM_TARGET = 5      /* N reached its target (inflx_solve_eom_to_efolds) */
+  INFLX_EOM_TARGET = 5      /* N reached its target (inflx_solve_eom_to_efolds); every sample was emitted (inflx_solve_eom_sampled) */
 } inflx_eom_status;
 int inflx_solve_eom(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps,
                     int method, double max_err, double dt, unsigned flags, double* states, double* t, double* efolds, int8_t* status,
@@ -464,6 +465,31 @@ int inflx_solve_eom(inflx_model* model, const double* p, size_t P, size_t n_p, c
 int inflx_solve_eom_to_efolds(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* target,
                               size_t max_steps, int method, double max_err, double dt, unsigned flags, double* states, double* t,
                               double* eps_h, double* efolds, int8_t* status);
+
+/*
+ * The state of B trajectories at every point of one list of samples shared by all of them: e-fold counts, or times with
+ * INFLX_EOM_SAMPLE_T.  The steps are inflx_solve_eom's; after every accepted step a lane emits the samples that step passed
+ * (sample <= N, or <= t, at the step's end), each located inside the step with the cubic Hermite interpolant of
+ * inflx_solve_eom_to_efolds: for N the sample's e-fold count exactly and t interpolated -- bit for bit what
+ * inflx_solve_eom_to_efolds returns for that target --, for t the sample's time exactly and N interpolated.  A sample equal to 0 is
+ * the initial state.  With INFLX_EOM_STOP_AT_END, in the step that ends inflation only the samples up to epsilon_H = 1 are emitted
+ * (N_s <= N_end; t_s <= t0 + f h with N_end's fraction f of the step), and a trajectory that is past the end at the start emits
+ * only a sample at 0.
+ *   p, P, n_p, init, B, method, max_err, dt    as for inflx_solve_eom
+ *   samples    (S,): finite, >= 0, strictly increasing; 1 <= S < 2^32
+ *   max_steps  accepted steps a trajectory may take
+ *   flags      INFLX_EOM_STOP_AT_END, INFLX_EOM_SAMPLE_T
+ *   out        (S, 8, B), trajectory fastest: phi^0, phi^1, chi^0, chi^1, H, N, t, epsilon_H at every sample; NaN for a sample that
+ *              the trajectory did not reach
+ *   efolds     (B,): N at epsilon_H = 1, meaningful for INFLX_EOM_ENDED;  n_stored (B,): the samples emitted (the first n_stored)
+ *   status     (B,): INFLX_EOM_TARGET once all S samples are emitted, INFLX_EOM_COMPLETE when max_steps ran out first, the other
+ *              codes as for inflx_solve_eom (INFLX_EOM_NONFINITE also when a located state is not finite)
+ * `efolds` and `n_stored` may be NULL.  Memory on the device is O(B S) for at most 2^28 bytes of samples per pass of lanes; every pass
+ * is copied into `out` as it is, with one strided copy.  Launches stop once no trajectory runs any more.
+ */
+int inflx_solve_eom_sampled(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* samples,
+                            size_t S, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds,
+                            int8_t* status, uint32_t* n_stored);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,7 @@ LAYOUT_AOS, LAYOUT_SOA = 0, 1
 SWEEP_DEFAULT, SWEEP_FORCE_TILE = 0, 1  # inflx_sweep_flags
 TIME_BACK_TO_BACK, TIME_DOMINANT_ONLY, TIME_IN_PIPELINE, TIME_SINGLE_CALL = range(4)  # inflx_timing
 EOM_RK4, EOM_RKF = 0, 1  # inflx_eom_method
-EOM_STOP_AT_END, EOM_FINAL_ONLY = 1, 2  # inflx_eom_flags
+EOM_STOP_AT_END, EOM_FINAL_ONLY, EOM_SAMPLE_T = 1, 2, 4  # inflx_eom_flags
 GATHER_PEER_PUSH, GATHER_RCCL = 0, 1  # inflx_gather: the exchange step of inflx_sweep_allgather_multi_ex
 
 _DP = C.POINTER(C.c_double)
@@ -108,6 +108,10 @@ SIGNATURES = {
     "inflx_solve_eom_to_efolds": (
         C.c_int,
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, _DP, C.POINTER(C.c_int8)],
+    ),
+    "inflx_solve_eom_sampled": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, C.POINTER(C.c_int8), C.POINTER(C.c_uint32)],
     ),
 }
 
@@ -473,6 +477,30 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return states, t, eps_h, efolds, status
+
+    def solve_eom_sampled(self, p, init, samples, max_steps: int, method: int, max_err: float, dt: float, flags: int):
+        """B trajectories from ``init`` (B,4) sampled at the points ``samples`` (S,) shared by all of them (include/inflx_hip.h:
+        inflx_solve_eom_sampled).  Returns (out (S, 8, B): y[0..5], t, epsilon_H at every sample, trajectory fastest; efolds; status
+        (int8); n_stored (uint32)).  ``flags``: ``EOM_STOP_AT_END``, ``EOM_SAMPLE_T``."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        samples = _f64(samples, "samples")
+        if samples.ndim != 1:
+            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        B, S = init.shape[0], samples.size
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((S, 8, B))
+        efolds = np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        n_stored = np.empty(B, dtype=np.uint32)
+        _check(
+            self._lib.inflx_solve_eom_sampled(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, _ptr(samples), S, int(max_steps), int(method), float(max_err), float(dt), int(flags),
+                _ptr(out), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)), n_stored.ctypes.data_as(C.POINTER(C.c_uint32)),
+            )
+        )  # fmt: skip
+        return out, efolds, status, n_stored
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

@@ -6,6 +6,7 @@ return value.  ``solve_eom_batch`` integrates many initial conditions or paramet
 counterpart of a consistency map from ``GeneralisedAL.complete_analysis`` over the same grid.  ``state_at_efolds`` returns the
 state at which a trajectory has made a given number of e-folds, and ``horizon_exit_map`` the state N_star e-folds before the end
 of inflation from every grid point: the (phi, chi, H) at which ``complete_analysis_ot`` and ``calc_V_array`` are evaluated.
+``solve_eom_sampled`` returns every trajectory's state at one list of e-fold counts (or times) shared by all of them.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -29,7 +30,8 @@ from . import _native
 from ._native import InflatoxShapeError
 from .compiler import CompilationArtifact
 
-__all__ = ["solve_eom", "solve_eom_batch", "efolds_map", "state_at_efolds", "horizon_exit_map", "EoMSolution", "EfoldsState", "STATUS"]
+__all__ = ["solve_eom", "solve_eom_batch", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
+           "SampledSolution", "STATUS"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -41,7 +43,7 @@ STATUS = {
     NONFINITE: "the state or the equations of motion at it are not finite",
     REJECTED: "50 consecutive rejected steps",
     UNDERFLOW: "the step size no longer moves t",
-    TARGET: "N reached its target (state_at_efolds, horizon_exit_map)",
+    TARGET: "N reached its target (state_at_efolds, horizon_exit_map); every sample was emitted (solve_eom_sampled)",
     ENDED_SHORT: "epsilon_H reached 1 after fewer than N_star e-folds (horizon_exit_map)",
 }
 _METHODS = {"rk4": _native.EOM_RK4, "rkf": _native.EOM_RKF}
@@ -69,6 +71,22 @@ class EfoldsState(NamedTuple):
     t: np.ndarray
     N: np.ndarray
     eps_H: np.ndarray
+    N_end: np.ndarray
+    status: np.ndarray
+
+
+class SampledSolution(NamedTuple):
+    """What :func:`solve_eom_sampled` returns.  ``states`` (B, S, 5): phi^0, phi^1, chi^0, chi^1, H at every sample; ``t``, ``N`` and
+    ``eps_H`` (B, S): cosmic time, e-folds and epsilon_H there -- all four are views of one (S, 8, B) array, trajectory fastest, and
+    NaN for a sample the trajectory did not reach; ``n_stored`` (B,): the samples emitted, always the first ``n_stored``; ``N_end``
+    (B,): N at epsilon_H = 1 of a trajectory that ENDED (``stop_at_end``), NaN otherwise; ``status`` (B,) int8: ``TARGET`` when all
+    S samples were emitted."""
+
+    states: np.ndarray
+    t: np.ndarray
+    N: np.ndarray
+    eps_H: np.ndarray
+    n_stored: np.ndarray
     N_end: np.ndarray
     status: np.ndarray
 
@@ -240,6 +258,45 @@ def state_at_efolds(artifact: CompilationArtifact, pars, fields_init, derivative
     hit = status == TARGET
     states = np.where(hit[:, None], states, np.nan)
     return EfoldsState(states[:, :5], np.where(hit, t, np.nan), states[:, 5], np.where(hit, eps, np.nan), np.where(status == ENDED, n_end, np.nan), status)
+
+
+def solve_eom_sampled(artifact: CompilationArtifact, pars, samples, fields_init, derivatives_init, max_steps: int = 100_000, max_err: float = 1e-8,
+                      solver: str = "rkf", *, at: str = "N", dt: float | None = None, stop_at_end: bool = True) -> SampledSolution:  # fmt: skip
+    """The state of B trajectories at every point of ``samples`` (S,), one list shared by all of them: e-fold counts (``at="N"``) or
+    cosmic times (``at="t"``), finite, >= 0 and strictly increasing.  ``fields_init``, ``derivatives_init``, ``pars``, ``solver``,
+    ``max_err`` and ``dt`` as for ``solve_eom_batch``; memory is O(B * S) and nothing is rearranged on the host.  The steps are those
+    of the ordinary run.  After every accepted step a trajectory emits the samples that step passed, each located inside the step
+    with the cubic Hermite interpolant of ``state_at_efolds`` (fourth order, like the steppers): for ``"N"`` the sample's N exactly
+    and t interpolated -- bit for bit ``state_at_efolds`` with that target --, for ``"t"`` the sample's t exactly and N
+    interpolated; epsilon_H is evaluated at the located state.  A sample equal to 0 is the initial state.  With ``stop_at_end``, in
+    the step where epsilon_H reaches 1 only the samples up to that point are emitted (``N_end`` as in ``efolds_map``), the rest are
+    NaN and the trajectory is ``ENDED``; one that starts past the end emits only a sample at 0.  ``status`` is ``TARGET`` once all
+    S samples are emitted, ``COMPLETE`` when ``max_steps`` accepted steps ran out first (``n_stored`` < S).  Bad arguments raise
+    before anything runs on the device."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    if at not in ("N", "t"):
+        raise ValueError(f"unknown sampling variable {at!r}: choose 'N' or 't'")
+    try:
+        pts = np.ascontiguousarray(samples, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("samples must be convertible to a float64 array") from None
+    if pts.ndim != 1:
+        raise InflatoxShapeError(f"samples must be one-dimensional (got shape {pts.shape})")
+    if pts.size < 1 or pts.size >= 2**32:
+        raise ValueError(f"the number of samples must be in [1, 2^32) (got {pts.size})")
+    if not (np.isfinite(pts).all() and (pts >= 0.0).all()):
+        raise ValueError("samples must be finite and >= 0")
+    if not (np.diff(pts) > 0.0).all():
+        raise ValueError("samples must be strictly increasing")
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    p = _pars(artifact, pars, x.shape[0])
+    init = np.concatenate([x, v], axis=1)
+    flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.EOM_SAMPLE_T if at == "t" else 0)
+    out, n_end, status, n_stored = _dylib(artifact).solve_eom_sampled(p, init, pts, max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
+    return SampledSolution(out[:, :5].transpose(2, 0, 1), out[:, 6].T, out[:, 5].T, out[:, 7].T, n_stored, np.where(status == ENDED, n_end, np.nan), status)
 
 
 def horizon_exit_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, derivatives_init=(0.0, 0.0),

@@ -319,3 +319,70 @@ INFLX_FN int inflx_bg_step_target(InflxBgLane& s, const double* __restrict__ p, 
   loc.t = t0 + th * h;
   return inflx_bg_located_epsilon(loc, p) ? INFLX_BG_TARGET : INFLX_BG_NONFINITE;
 }
+
+// ---- samples: the state at every point of a list shared by all lanes ------------------------------------------------------------
+// `samples` (n_samples, finite, >= 0, strictly increasing) are e-fold counts, or times when `sample_t`.  A lane emits sample k --
+// sink(k, located state) -- from the accepted step that passes it, with the dense output above: for N the theta of
+// inflx_bg_locate, N = the sample exactly and t = t0 + theta h, which is inflx_bg_step_target's located state bit for bit; for t,
+// theta = (t_s - t0) / h, t = the sample exactly and N from the interpolant.  `cursor` counts the samples emitted.  The lane goes on
+// from the step's end state, never from a located one, so its steps are those of the ordinary run.
+
+// inflx_bg_init for a lane with samples: a sample equal to 0 is the initial state (also of a lane that is already past the end of
+// inflation, which ends here as in inflx_bg_init); INFLX_BG_TARGET when that was the only sample.
+template <class SINK>
+INFLX_FN int inflx_bg_init_sampled(InflxBgLane& s, const double* init, const double* __restrict__ p, double dt0, bool stop_at_end,
+                                   const double* __restrict__ samples, unsigned n_samples, unsigned& cursor, double& n_end, SINK& sink) {
+  cursor = 0;
+  const int st = inflx_bg_init(s, init, p, dt0, stop_at_end, n_end);
+  if (st == INFLX_BG_NONFINITE) return st;
+  if (n_samples > 0 && samples[0] == 0.0) {
+    InflxBgLocated loc;
+    for (int c = 0; c < 6; ++c) loc.y[c] = s.y[c];
+    loc.t = s.t;
+    loc.eps = inflx_bg_epsilon(s);
+    sink(0u, loc);
+    cursor = 1;
+  }
+  return st == INFLX_BG_RUNNING && cursor == n_samples ? INFLX_BG_TARGET : st;
+}
+
+// One accepted step of a lane with samples, and every sample that step passed: those with sample <= N1 (<= t1 when sample_t).  In
+// the step that ends inflation (stop_at_end) only the samples up to epsilon_H = 1 are emitted -- N_s <= n_end, or
+// t_s <= t0 + f h with n_end's fraction f = (1 - eps0) / (eps1 - eps0) --, inflx_bg_step_target's "which comes first".  Returns
+// INFLX_BG_TARGET once every sample is emitted, INFLX_BG_NONFINITE when a located state is not finite (that sample is not emitted),
+// and inflx_bg_step_taken's status otherwise.
+template <int METHOD, class SINK>
+INFLX_FN int inflx_bg_step_sampled(InflxBgLane& s, const double* __restrict__ p, double max_err, double fixed_dt, bool stop_at_end,
+                                   const double* __restrict__ samples, unsigned n_samples, bool sample_t, unsigned& cursor, double& n_end,
+                                   SINK& sink) {
+  double y0[6], f0[6], h = 0.0;
+  for (int c = 0; c < 6; ++c) {
+    y0[c] = s.y[c];
+    f0[c] = s.f[c];
+  }
+  const double t0 = s.t, eps0 = inflx_bg_epsilon(s);
+  const int st = inflx_bg_step_taken<METHOD>(s, p, max_err, fixed_dt, stop_at_end, n_end, h);
+  if (st != INFLX_BG_RUNNING && st != INFLX_BG_ENDED) return st;
+  double t_end = 0.0;  // t at epsilon_H = 1 (sample_t, in the step that ends inflation)
+  if (st == INFLX_BG_ENDED && sample_t) t_end = t0 + (1.0 - eps0) / (inflx_bg_epsilon(s) - eps0) * h;
+  while (cursor < n_samples) {
+    const double x = samples[cursor];
+    if (sample_t ? !(x <= s.t) : !(s.y[5] >= x)) break;
+    if (st == INFLX_BG_ENDED && (sample_t ? t_end < x : n_end < x)) break;
+    InflxBgLocated loc;
+    if (sample_t) {
+      const double th = (x - t0) / h;
+      for (int c = 0; c < 6; ++c) loc.y[c] = inflx_bg_hermite(y0[c], f0[c], s.y[c], s.f[c], h, th);
+      loc.t = x;
+    } else {
+      const double th = inflx_bg_locate(y0[5], f0[5], s.y[5], s.f[5], h, x);
+      for (int c = 0; c < 5; ++c) loc.y[c] = inflx_bg_hermite(y0[c], f0[c], s.y[c], s.f[c], h, th);
+      loc.y[5] = x;
+      loc.t = t0 + th * h;
+    }
+    if (!inflx_bg_located_epsilon(loc, p)) return INFLX_BG_NONFINITE;
+    sink(cursor, loc);
+    ++cursor;
+  }
+  return cursor == n_samples ? INFLX_BG_TARGET : st;
+}

@@ -7,7 +7,7 @@
 
 // (overridable with -DINFLX_BG_ABI_VERSION=<n> so that a test can build an object of another layout version and see it refused)
 #ifndef INFLX_BG_ABI_VERSION
-#define INFLX_BG_ABI_VERSION 3
+#define INFLX_BG_ABI_VERSION 4
 #endif
 // the artefact ABI major a background object reports by default: the core object's (csrc/inflx_sweep_kernels.hip, overridable there
 // and here with -DINFLX_ABI_VERSION_MAJOR, which the background object is built with whenever the core object is)
@@ -20,7 +20,7 @@ enum InflxBgCarry {
   INFLX_BG_CARRY_DT = 7,
   INFLX_BG_CARRY_NEND = 8,      // N at epsilon_H = 1 (NaN until the lane ends there)
   INFLX_BG_CARRY_STATUS = 9,
-  INFLX_BG_CARRY_LAST_ROW = 10, // index of the last row that holds a state
+  INFLX_BG_CARRY_LAST_ROW = 10, // index of the last row that holds a state (*_sampled kernels: the number of samples emitted)
   INFLX_BG_CARRY_PENDING = 11,  // 1: the lane ended inside a row that has not been written yet (that row holds the end state)
   INFLX_BG_CARRY_ROW_PLANES = 12,  // the planes inflx_solve_eom reads back
   INFLX_BG_CARRY_EPS = 12,      // epsilon_H at the located state of a lane that reached its target on N (NaN otherwise)
@@ -31,28 +31,33 @@ enum InflxBgCarry {
 // [step_begin, step_begin + steps) of every lane -- the same indices for all lanes, whether they still run or not --, and row r is
 // complete after step index r*substeps - 1; it goes to slot r - row_base of `rows`.  The *_target kernels (final-only, substeps = 1)
 // stop a lane at its target on N as well: the lane's carry then holds the located state (planes Y, T, EPS).  They skip a lane that
-// has stopped, and add the number of lanes still running after the launch to *running.
+// has stopped, and add the number of lanes still running after the launch to *running.  So do the *_sampled kernels (final-only,
+// substeps = 1), whose lanes emit the state at every point of `samples` that an accepted step passes into `rows`, here planes
+// [sample][8][n]: y[0..5], t, epsilon_H; the lane's cursor into `samples` is its carry plane LAST_ROW.  The host fills `rows` with NaN
+// first: a sample that a lane never reaches stays NaN.
 struct InflxBgArgs {
   const double* p;       // parameter rows of lane 0 of this launch
   uint64_t p_stride;     // doubles between the parameter rows of two lanes (0: one row for all)
   const double* init;    // (n, 4): phi^0, phi^1, chi^0, chi^1 (init kernel)
   double* carry;         // [INFLX_BG_CARRY_PLANES][n]
-  double* rows;          // [slot][7][n]: y[0..5], t -- or NULL
+  double* rows;          // [slot][7][n]: y[0..5], t -- or NULL (*_sampled kernels: [sample][8][n], with epsilon_H)
   uint64_t n;            // lanes
   uint64_t step_begin;   // first accepted-step index of this launch
   uint64_t row_base;     // row held by slot 0 of `rows`
   uint32_t steps;        // accepted-step indices this launch processes (at most INFLX_BG_STEPS_PER_LAUNCH)
   uint32_t substeps;     // accepted steps per row
-  uint32_t flags;        // bit 0: stop at epsilon_H = 1
-  uint32_t reserved;
+  uint32_t flags;        // bit 0: stop at epsilon_H = 1; bit 1: `samples` are times, not e-fold counts
+  uint32_t n_samples;    // points in `samples`
   double max_err;
   double fixed_dt;       // > 0: fixed step
   const double* target;  // (n,): the target on N of every lane (init and *_target kernels) -- or NULL
-  uint32_t* running;     // *_target kernels: one word, += the lanes still running when the launch ends
+  uint32_t* running;     // *_target and *_sampled kernels: one word, += the lanes still running when the launch ends
+  const double* samples; // (n_samples,): the sample points of all lanes, strictly increasing (init and *_sampled kernels) -- or NULL
 };
-static_assert(sizeof(InflxBgArgs) == 112, "InflxBgArgs layout");
+static_assert(sizeof(InflxBgArgs) == 120, "InflxBgArgs layout");
 static_assert(offsetof(InflxBgArgs, step_begin) == 48 && offsetof(InflxBgArgs, steps) == 64 && offsetof(InflxBgArgs, max_err) == 80 &&
-                  offsetof(InflxBgArgs, target) == 96 && offsetof(InflxBgArgs, running) == 104,
+                  offsetof(InflxBgArgs, n_samples) == 76 && offsetof(InflxBgArgs, target) == 96 && offsetof(InflxBgArgs, running) == 104 &&
+                  offsetof(InflxBgArgs, samples) == 112,
               "InflxBgArgs layout");
 
 // bound of one launch: accepted steps per lane (each of at most 50 trials)

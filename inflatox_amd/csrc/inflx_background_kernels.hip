@@ -11,7 +11,9 @@
 // Rows go to `rows`, planes [row][7][n]: y[0..5], t -- lane fastest, so that a wavefront's store of one component is 512 contiguous
 // bytes.  STORE_ROWS = false is the final-only mode (e-fold maps): nothing but the carry is written.  TARGET = true (final-only)
 // adds a per-lane target on N: a lane stops at the state where N = target, located inside the accepted step that passes it
-// (inflx_bg_step_target), and that state -- with epsilon_H there -- is what its carry holds.
+// (inflx_bg_step_target), and that state -- with epsilon_H there -- is what its carry holds.  The *_sampled kernels (final-only)
+// emit the state at every point of a list of e-fold counts or times shared by all lanes (inflx_bg_step_sampled) into planes
+// [sample][8][n]: y[0..5], t, epsilon_H.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -56,6 +58,19 @@ __device__ __forceinline__ void store_row(double* rows, uint64_t n, uint32_t slo
   base[6u * n] = valid ? t : nan;
 }
 
+// sample `k` of one lane: the located state, its time and epsilon_H there
+struct SampleSink {
+  double* base;  // plane 0 of sample 0, at this lane
+  uint64_t n;
+  __device__ __forceinline__ void operator()(unsigned k, const InflxBgLocated& loc) const {
+    double* out = base + (uint64_t)k * 8u * n;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) out[(uint64_t)c * n] = loc.y[c];
+    out[6u * n] = loc.t;
+    out[7u * n] = loc.eps;
+  }
+};
+
 extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_init(const InflxBgArgs a) {
   const uint64_t lane = (uint64_t)blockIdx.x * kBgThreads + threadIdx.x;
   if (lane >= a.n) return;
@@ -67,8 +82,15 @@ extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_init(const Inf
   const double dt0 = a.fixed_dt > 0.0 ? a.fixed_dt : INFLX_BG_FIRST_DT;
   InflxBgLocated loc;
   loc.eps = __builtin_nan("");
-  const int st = a.target ? inflx_bg_init_target(s, init, p, dt0, (a.flags & 1u) != 0, a.target[lane], n_end, loc)
-                          : inflx_bg_init(s, init, p, dt0, (a.flags & 1u) != 0, n_end);
+  unsigned cursor = 0;  // (lanes with samples: the samples emitted)
+  int st;
+  if (a.samples) {
+    SampleSink sink{a.rows + lane, a.n};
+    st = inflx_bg_init_sampled(s, init, p, dt0, (a.flags & 1u) != 0, a.samples, a.n_samples, cursor, n_end, sink);
+  } else {
+    st = a.target ? inflx_bg_init_target(s, init, p, dt0, (a.flags & 1u) != 0, a.target[lane], n_end, loc)
+                  : inflx_bg_init(s, init, p, dt0, (a.flags & 1u) != 0, n_end);
+  }
   double* cy = a.carry + lane;
   for (int c = 0; c < 6; ++c) cy[(uint64_t)(INFLX_BG_CARRY_Y + c) * a.n] = s.y[c];
   cy[(uint64_t)INFLX_BG_CARRY_EPS * a.n] = loc.eps;
@@ -76,9 +98,9 @@ extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_init(const Inf
   cy[(uint64_t)INFLX_BG_CARRY_DT * a.n] = s.dt;
   cy[(uint64_t)INFLX_BG_CARRY_NEND * a.n] = n_end;
   cy[(uint64_t)INFLX_BG_CARRY_STATUS * a.n] = (double)st;
-  cy[(uint64_t)INFLX_BG_CARRY_LAST_ROW * a.n] = 0.0;
+  cy[(uint64_t)INFLX_BG_CARRY_LAST_ROW * a.n] = (double)cursor;
   cy[(uint64_t)INFLX_BG_CARRY_PENDING * a.n] = 0.0;
-  if (a.rows) store_row(a.rows, a.n, 0, lane, s.y, s.t, true);  // row 0 (slot 0) is the initial state
+  if (a.rows && !a.samples) store_row(a.rows, a.n, 0, lane, s.y, s.t, true);  // row 0 (slot 0) is the initial state
 }
 
 // A running lane with a target on N: at most a.steps accepted steps; true while it still runs.  A lane that stops keeps in its
@@ -104,6 +126,31 @@ __device__ __forceinline__ bool advance_to_target(const InflxBgArgs& a, uint64_t
   cy[(uint64_t)INFLX_BG_CARRY_NEND * a.n] = n_end;
   cy[(uint64_t)INFLX_BG_CARRY_STATUS * a.n] = (double)status;
   if (located) cy[(uint64_t)INFLX_BG_CARRY_EPS * a.n] = loc.eps;
+  return status == INFLX_BG_RUNNING;
+}
+
+// A running lane with samples: at most a.steps accepted steps, every sample they pass stored; true while it still runs.  The carry
+// holds the state the lane integrates from (never a located one) and, in plane LAST_ROW, the number of samples emitted.
+template <int METHOD>
+__device__ __forceinline__ bool advance_sampled(const InflxBgArgs& a, uint64_t lane, const double* p, double* cy) {
+  InflxBgLane s;
+  for (int c = 0; c < 6; ++c) s.y[c] = cy[(uint64_t)(INFLX_BG_CARRY_Y + c) * a.n];
+  s.t = cy[(uint64_t)INFLX_BG_CARRY_T * a.n];
+  s.dt = cy[(uint64_t)INFLX_BG_CARRY_DT * a.n];
+  double n_end = cy[(uint64_t)INFLX_BG_CARRY_NEND * a.n];
+  unsigned cursor = (unsigned)cy[(uint64_t)INFLX_BG_CARRY_LAST_ROW * a.n];
+  const bool stop_at_end = (a.flags & 1u) != 0, sample_t = (a.flags & 2u) != 0;
+  inflx_bg_resume(s, p);
+  SampleSink sink{a.rows + lane, a.n};
+  int status = INFLX_BG_RUNNING;
+  for (uint32_t i = 0; i < a.steps && status == INFLX_BG_RUNNING; ++i)
+    status = inflx_bg_step_sampled<METHOD>(s, p, a.max_err, a.fixed_dt, stop_at_end, a.samples, a.n_samples, sample_t, cursor, n_end, sink);
+  for (int c = 0; c < 6; ++c) cy[(uint64_t)(INFLX_BG_CARRY_Y + c) * a.n] = s.y[c];
+  cy[(uint64_t)INFLX_BG_CARRY_T * a.n] = s.t;
+  cy[(uint64_t)INFLX_BG_CARRY_DT * a.n] = s.dt;
+  cy[(uint64_t)INFLX_BG_CARRY_NEND * a.n] = n_end;
+  cy[(uint64_t)INFLX_BG_CARRY_STATUS * a.n] = (double)status;
+  cy[(uint64_t)INFLX_BG_CARRY_LAST_ROW * a.n] = (double)cursor;
   return status == INFLX_BG_RUNNING;
 }
 
@@ -172,3 +219,18 @@ INFLX_BG_KERNEL(inflx_bg_advance_rkf_rows, INFLX_BG_RKF, true, false)
 INFLX_BG_KERNEL(inflx_bg_advance_rkf_final, INFLX_BG_RKF, false, false)
 INFLX_BG_KERNEL(inflx_bg_advance_rk4_target, INFLX_BG_RK4, false, true)
 INFLX_BG_KERNEL(inflx_bg_advance_rkf_target, INFLX_BG_RKF, false, true)
+
+// *_sampled: a lane that has stopped is left as it is; every wavefront adds its lanes that still run to *a.running
+template <int METHOD>
+__device__ __forceinline__ void advance_samples(const InflxBgArgs& a) {
+  const uint64_t lane = (uint64_t)blockIdx.x * kBgThreads + threadIdx.x;
+  if (lane >= a.n) return;
+  double* cy = a.carry + lane;
+  const bool was_running = (int)cy[(uint64_t)INFLX_BG_CARRY_STATUS * a.n] == INFLX_BG_RUNNING;
+  bool runs_on = false;
+  if (was_running) runs_on = advance_sampled<METHOD>(a, lane, a.p + lane * a.p_stride, cy);
+  const unsigned long long mask = __ballot(runs_on);
+  if ((threadIdx.x & 63u) == 0u && mask != 0ull) atomicAdd(a.running, (uint32_t)__popcll(mask));
+}
+extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_advance_rk4_sampled(const InflxBgArgs a) { advance_samples<INFLX_BG_RK4>(a); }
+extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_advance_rkf_sampled(const InflxBgArgs a) { advance_samples<INFLX_BG_RKF>(a); }

@@ -419,6 +419,7 @@ struct inflx_model {
   hipFunction_t bg_init = nullptr;
   hipFunction_t bg_advance[2][2] = {};  // [method][store rows]
   hipFunction_t bg_target[2] = {};      // [method]: final-only with a target on N (inflx_solve_eom_to_efolds)
+  hipFunction_t bg_sampled[2] = {};     // [method]: final-only with a list of samples (inflx_solve_eom_sampled)
 };
 
 namespace {
@@ -2778,16 +2779,20 @@ int need_background(inflx_model* m) {
                      path.c_str(), m->path.c_str(), tag, m->tag.c_str()));
   const char* names[2][2] = {{"inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows"}, {"inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows"}};
   const char* target_names[2] = {"inflx_bg_advance_rk4_target", "inflx_bg_advance_rkf_target"};
-  hipFunction_t init = nullptr, adv[2][2] = {}, tgt[2] = {};
+  const char* sampled_names[2] = {"inflx_bg_advance_rk4_sampled", "inflx_bg_advance_rkf_sampled"};
+  hipFunction_t init = nullptr, adv[2][2] = {}, tgt[2] = {}, smp[2] = {};
   if (hipModuleGetFunction(&init, module, "inflx_bg_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_bg_init", path.c_str()));
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b)
       if (hipModuleGetFunction(&adv[a][b], module, names[a][b]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a][b]));
   for (int a = 0; a < 2; ++a)
     if (hipModuleGetFunction(&tgt[a], module, target_names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), target_names[a]));
+  for (int a = 0; a < 2; ++a)
+    if (hipModuleGetFunction(&smp[a], module, sampled_names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), sampled_names[a]));
   m->bg_module = module;
   m->bg_init = init;
   for (int a = 0; a < 2; ++a) m->bg_target[a] = tgt[a];
+  for (int a = 0; a < 2; ++a) m->bg_sampled[a] = smp[a];
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b) m->bg_advance[a][b] = adv[a][b];
   note_sf_word(m, module);
@@ -2796,10 +2801,10 @@ int need_background(inflx_model* m) {
 
 // device buffers of one call, released on every way out
 struct BgBuffers {
-  double *p = nullptr, *init = nullptr, *carry = nullptr, *rows = nullptr, *target = nullptr;
+  double *p = nullptr, *init = nullptr, *carry = nullptr, *rows = nullptr, *target = nullptr, *samples = nullptr;
   uint32_t* running = nullptr;
   ~BgBuffers() {
-    for (double* d : {p, init, carry, rows, target})
+    for (double* d : {p, init, carry, rows, target, samples})
       if (d) (void)hipFree(d);
     if (running) (void)hipFree(running);
   }
@@ -3000,6 +3005,102 @@ int inflx_solve_eom_to_efolds(inflx_model* m, const double* p, size_t P, size_t 
       if (states)
         for (int c = 0; c < 6; ++c) states[(c0 + l) * 6 + c] = hc[(size_t)(INFLX_BG_CARRY_Y + c) * n + l];
       if (t) t[c0 + l] = hc[INFLX_BG_CARRY_T * n + l];
+    }
+  }
+  return sf_verdict(m);
+}
+
+int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* samples, size_t S,
+                            size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status,
+                            uint32_t* n_stored) {
+  INFLX_SERIALISE(m);
+  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the background solver requires a 2-field model (model has %u fields)", m->dim);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
+  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
+  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
+  if (flags & ~(unsigned)(INFLX_EOM_STOP_AT_END | INFLX_EOM_SAMPLE_T)) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
+  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
+  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
+  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  if (S < 1 || (uint64_t)S > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of samples must be in [1, 2^32) (got %zu)", S);
+  if (!samples) return fail(INFLX_ERR_ARG, "sample array is NULL");
+  for (size_t k = 0; k < S; ++k) {
+    if (!std::isfinite(samples[k]) || samples[k] < 0.0) return fail(INFLX_ERR_ARG, "sample %zu is not a finite number >= 0", k);
+    if (k && !(samples[k] > samples[k - 1])) return fail(INFLX_ERR_ARG, "samples must be strictly increasing (sample %zu is not above sample %zu)", k, k - 1);
+  }
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  int rc = need_background(m);
+  if (rc) return rc;
+  hipStream_t s = m->stream;
+  // lanes reach a sample in different launches, so the device buffer holds all S samples of a pass's lanes: the lanes of a pass are
+  // bounded by the row buffer's bytes (whole workgroups where more than one fits)
+  size_t nc_max = std::max<size_t>(1, kBgRowBytes / (8 * sizeof(double) * S));
+  if (nc_max > 256) nc_max -= nc_max % 256;
+  nc_max = std::min({B, kBgMaxLanes, nc_max});
+  const size_t plane_bytes = S * 8 * sizeof(double);  // (of one lane)
+  BgBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.samples), S * sizeof(double)));
+  HIP_TRY(hipMemcpyAsync(buf.samples, samples, S * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.rows), nc_max * plane_bytes));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  std::vector<double> host_carry(nc_max * INFLX_BG_CARRY_ROW_PLANES);
+  hipFunction_t advance = m->bg_sampled[method == INFLX_EOM_RKF ? 1 : 0];
+
+  for (size_t c0 = 0; c0 < B; c0 += nc_max) {
+    const size_t n = std::min(nc_max, B - c0);
+    InflxBgArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = buf.init;
+    a.carry = buf.carry;
+    a.rows = buf.rows;
+    a.n = n;
+    a.substeps = 1;
+    a.flags = ((flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u) | ((flags & INFLX_EOM_SAMPLE_T) ? 2u : 0u);
+    a.n_samples = (uint32_t)S;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    a.running = buf.running;
+    a.samples = buf.samples;
+    void* params[] = {&a};
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    // every byte 0xff: each double is a NaN, which a sample that its lane never reaches keeps
+    HIP_TRY(hipMemsetAsync(buf.rows, 0xff, n * plane_bytes, s));
+    HIP_TRY(hipModuleLaunchKernel(m->bg_init, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    // launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
+    for (uint64_t step = 0; step < (uint64_t)max_steps;) {
+      const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
+      a.step_begin = step;
+      a.steps = (uint32_t)k;
+      uint32_t running = 0;
+      HIP_TRY(hipMemsetAsync(buf.running, 0, sizeof(uint32_t), s));
+      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+      HIP_TRY(hipMemcpyAsync(&running, buf.running, sizeof running, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      step += k;
+      if (running == 0) break;
+    }
+    // the planes as they are: plane (sample, component) of this pass's lanes is n doubles, B doubles apart in `out`
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.rows, n * sizeof(double), n * sizeof(double), 8 * S, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_ROW_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double* hc = host_carry.data();
+    for (size_t l = 0; l < n; ++l) {
+      status[c0 + l] = (int8_t)hc[INFLX_BG_CARRY_STATUS * n + l];
+      if (efolds) efolds[c0 + l] = hc[INFLX_BG_CARRY_NEND * n + l];
+      if (n_stored) n_stored[c0 + l] = (uint32_t)hc[INFLX_BG_CARRY_LAST_ROW * n + l];
     }
   }
   return sf_verdict(m);

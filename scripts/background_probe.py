@@ -8,8 +8,10 @@ rows stored or copied: kernels plus one carry copy) for B in {2^14, 2^17, 2^20},
     rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/background_probe.py --quick
 
 (kernels ``inflx_bg_advance_*``).  ``--horizon-exit`` times nothing but ``horizon_exit_map`` beside ``efolds_map`` on the same
-1024^2 hyperbolic grid (best of three calls each, after a warm-up) and writes ``profiles/background_horizon_exit.json``.  Run from
-the repository root on the GPU box.
+1024^2 hyperbolic grid (best of three calls each, after a warm-up) and writes ``profiles/background_horizon_exit.json``.
+``--sampled`` times nothing but ``solve_eom_sampled`` at B = 2^17 with S = 256 e-fold counts beside ``solve_eom_batch`` returning 256
+rows of the same trajectories (three calls each, alternating, after a warm-up of both) and writes
+``profiles/background_sampled.json``.  Run from the repository root on the GPU box.
 """
 
 import argparse
@@ -83,14 +85,52 @@ def horizon_exit(n=1024, n_star=1.0, repeats=3):
         json.dump(rec, fh, indent=1)
 
 
+def sampled(log2_lanes=17, n_samples=256, rows=256, substeps=4, repeats=3, seed=0):
+    spec, art = workloads.artifact_for("hyperbolic")
+    (a0, b0), (a1, b1), vel = START["hyperbolic"]
+    B = 1 << log2_lanes
+    rng = np.random.default_rng(seed)
+    x = np.stack([rng.uniform(a0, b0, B), rng.uniform(a1, b1, B)], axis=1)
+    v = rng.uniform(-vel, vel, (B, 2))
+    samples = np.linspace(0.0, 4.0, n_samples)
+    kw = dict(max_err=1e-6, solver="rkf")
+    background.solve_eom_sampled(art, spec.args, samples, x[:256], v[:256], **kw)  # build / load / warm up
+    background.solve_eom_batch(art, spec.args, 4, x[:256], v[:256], substeps=substeps, **kw)
+    t_sampled, t_rows = [], []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        sol = background.solve_eom_sampled(art, spec.args, samples, x, v, **kw)
+        t_sampled.append(time.perf_counter() - t0)
+        stored = int(sol.n_stored.sum())
+        status = {int(k): int(c) for k, c in zip(*np.unique(sol.status, return_counts=True))}
+        del sol
+        t0 = time.perf_counter()
+        ref = background.solve_eom_batch(art, spec.args, rows, x, v, substeps=substeps, **kw)
+        t_rows.append(time.perf_counter() - t0)
+        row_steps = int(np.sum(np.minimum(ref.last_row, rows - 1))) * substeps
+        del ref
+    rec = dict(model="hyperbolic", code_object=art._build[2], B=B, samples=n_samples, sample_range=[0.0, 4.0], at="N", stop_at_end=True, solver="rkf",
+               max_err=1e-6, repeats=repeats, solve_eom_sampled_s=t_sampled, samples_stored=stored, sampled_status_counts=status,
+               solve_eom_batch_rows=rows, solve_eom_batch_substeps=substeps, solve_eom_batch_s=t_rows, solve_eom_batch_accepted_lane_steps=row_steps,
+               note="wall time of whole calls; the two calls return different things (states at shared e-fold counts against every fourth accepted step), so this is a comparison of two ways to get 256 states per trajectory, not of the same work",
+               command="python scripts/background_probe.py --sampled")  # fmt: skip
+    print(json.dumps(rec), flush=True)
+    with open(os.path.join(ROOT, "profiles", "background_sampled.json"), "w") as fh:
+        json.dump(rec, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sampled", action="store_true", help="time solve_eom_sampled (B = 2^17, S = 256) beside solve_eom_batch returning 256 rows, nothing else")
     ap.add_argument("--horizon-exit", action="store_true", help="time horizon_exit_map beside efolds_map at 1024^2 on hyperbolic, nothing else")
     ap.add_argument("--quick", action="store_true", help="B = 2^14 only (for a profiler run)")
     ap.add_argument("--max-log2-lanes", type=int, default=20)
     args = ap.parse_args()
     if args.horizon_exit:
         horizon_exit()
+        return
+    if args.sampled:
+        sampled()
         return
     sizes = [14] if args.quick else [k for k in (14, 17, 20) if k <= args.max_log2_lanes]
     for name in ("hyperbolic", "egno"):
