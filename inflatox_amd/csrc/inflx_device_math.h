@@ -37,15 +37,24 @@ INFLX_FN double inflx_ipow(double x) {
   }
 }
 
-// x^(N/2) for odd N >= 1: x^((N-1)/2) * sqrt(x).  sqrt of a negative base yields NaN exactly like
-// pow(x, N/2.0) does.
+// x^(N/2) for odd N >= 1: x^((N-1)/2) * sqrt(x).  sqrt of a finite negative base yields NaN exactly like
+// pow(x, N/2.0) does.  At the two negative arguments that are not "less than zero" pow goes by the magnitude of
+// the base -- pow(-0.0, N/2.0) = +0 and pow(-inf, N/2.0) = +inf (C99 F.9.4.4) -- where the product gives
+// (-0)^k * (-0), which is -0 for even k, and NaN (sqrt(-inf)).  inflx_hpow_edges puts that right on the RESULT:
+// its magnitude (the product is positive or NaN for every other argument, so no other value changes; a NaN
+// may lose its sign bit), and +inf for x = -inf.  On the result and not on the base, so that sqrt(x) stays the
+// expression other statements of a model share: counted in the disassembly of EGNO's tile kernel with this
+// toolchain (scripts/kernel_resources.py egno; not timed), a corrected base costs a second root, 26 VALU
+// instructions per point, the selection on the result about 3 per half power (row loop 608 -> 618).  The
+// printer's 1.0/inflx_hpow<N>(x) then is +inf at -0.0 and +0 at -inf like pow(x, -N/2.0).
+INFLX_FN double inflx_hpow_edges(double x, double p) { return x == -__builtin_inf() ? __builtin_inf() : __builtin_fabs(p); }
 template <int N>
 INFLX_FN double inflx_hpow(double x) {
   static_assert(N >= 1 && (N % 2) == 1, "inflx_hpow needs an odd positive numerator");
   if constexpr (N == 1) {
-    return sqrt(x);
+    return inflx_hpow_edges(x, sqrt(x));
   } else {
-    return inflx_ipow<(N - 1) / 2>(x) * sqrt(x);
+    return inflx_hpow_edges(x, inflx_ipow<(N - 1) / 2>(x) * sqrt(x));
   }
 }
 
@@ -65,9 +74,12 @@ INFLX_FN double inflx_hpow(double x) {
 // The three operations are only valid while nothing overflows or underflows on the way.  ONE comparison per
 // quotient establishes that (4.8 fma-equivalents per quotient in all, against 13.0):
 //   * inflx_recip hands over y = NaN unless 2^-500 <= |b| <= 2^500 (evaluated in the earlier stage);
-//   * the quotient is accepted iff |q| >= 2^-400.  Then |a| >= 2^-901, so the residual a - b*q0 is a multiple
+//   * the quotient is accepted iff 2^-400 <= |q| < infinity.  Then |a| >= 2^-901, so the residual a - b*q0 is a multiple
 //     of 2^-1006 and exact; an infinite or NaN numerator, an overflowing product a*y and a NaN reciprocal all
-//     end as q = NaN, which fails the comparison; zero, tiny and denormal quotients fail it by magnitude.
+//     end as q = NaN, which fails the comparison; zero, tiny and denormal quotients fail it by magnitude.  The upper
+//     end is for the quotient that overflows in the LAST step only: a*y can round to a finite q0 just below the
+//     threshold where a/b rounds to infinity (a = 2^1024 * b: about one b in seven), and q0 + r*y then is +-inf --
+//     RN(a/b) as it happens, but not a regular case (tests/device_math_probe.hip).
 // A quotient that is not accepted clears `ok`: the tile kernel then evaluates that grid row again with IEEE
 // divisions (inflx_stage_point_ieee), so the stored values are those of the IEEE program always.  Rows inside
 // a NaN region of the model are evaluated twice for that reason -- correct, merely slower there.
@@ -98,7 +110,7 @@ INFLX_FN double inflx_div_by_hoisted(double a, double b, double y, bool& ok) {
   const double r = __builtin_fma(-b, q0, a);
   const double q = __builtin_fma(r, y, q0);
 #ifndef INFLX_DIVH_TRUST  // (experiments only: time the hot loop as if every quotient were accepted)
-  ok = ok && (__builtin_fabs(q) >= 0x1p-400);
+  ok = ok && (__builtin_fabs(q) >= 0x1p-400) && (__builtin_fabs(q) < __builtin_inf());
 #endif
   return q;
 }
@@ -134,7 +146,7 @@ INFLX_FN double inflx_div_by_hoisted_inline(double a, double b, double y) {
 // quotient is exactly what the eight arithmetic instructions deliver (inflx_ops.h has the argument in full) -- and the
 // five of the reciprocal depend on the denominator alone: quotients with the same denominator share them and cost
 // three instructions and one comparison each instead of eleven.  "Mid range" is tested, not assumed: the denominator's
-// exponent field once per reciprocal (2^-500 <= |b| < 2^501), |q| >= 2^-400 per quotient (a NaN, an infinity, an
+// exponent field once per reciprocal (2^-500 <= |b| < 2^501), 2^-400 <= |q| < infinity per quotient (a NaN, an infinity, an
 // overflow or a zero anywhere fail one of the two); a point that fails clears `ok` and the tile kernel evaluates its
 // grid row again with the compiler's divisions, so the stored values are the IEEE program's always.
 #ifndef INFLX_HOST_TWIN
@@ -147,7 +159,7 @@ INFLX_FN double inflx_shared_reciprocal(double b, bool& ok) {
 INFLX_FN double inflx_div_by_shared(double a, double b, double y, bool& ok) {
   const double q0 = a * y;
   const double q = __builtin_fma(__builtin_fma(-b, q0, a), y, q0);
-  ok = ok && (__builtin_fabs(q) >= 0x1p-400);
+  ok = ok && (__builtin_fabs(q) >= 0x1p-400) && (__builtin_fabs(q) < __builtin_inf());
   return q;
 }
 #else

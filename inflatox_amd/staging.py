@@ -146,8 +146,10 @@ class HIPInflatoxPrinter(C99CodePrinter):
             if n == -1:
                 # a stand-alone x**(-1/2) (inside a product sympy prints 1/sqrt(x) itself; on its own --
                 # e.g. as a cse definition -- C99 gets pow(x, -1.0/2.0), compiler.py:403-408): one sqrt and
-                # one division instead of the general pow; `+ 0.0` keeps pow's +inf at x = -0.0
-                return f"(1.0/sqrt({self._print(base)} + 0.0))"
+                # one division instead of the general pow; inflx_hpow<1> is sqrt(x) with pow's results at the
+                # two edges (csrc/inflx_device_math.h: +0 at x = -0.0, +inf at x = -inf), so that the quotient is
+                # pow's +inf at x = -0.0 and its +0 at x = -inf
+                return f"(1.0/inflx_hpow<1>({self._print(base)}))"
         return super()._print_Pow(expr)
 
     # -- special functions (reference: GSLInflatoxPrinter, compiler.py:123-212 -> gsl_sf_bessel_*) ------

@@ -201,14 +201,17 @@ def test_solve_eom_signature_is_the_references():
     assert [(q.name, q.default) for q in params if q.kind == q.KEYWORD_ONLY] == [("dt", None)]
 
 
-# core content tags of the example models at the commit before the background solver: the sweep objects, profiles/ stamps and
-# bench.py figures are untouched only if these stay as they are
+# core content tags of the example models: the sweep objects, profiles/ stamps and bench.py figures are untouched only if these
+# stay as they are.  Last moved on purpose by the change of csrc/inflx_device_math.h that gives the half powers pow's results at
+# -0.0 and -inf and the hoisted / shared quotients an upper end of their acceptance test (the tag covers the csrc headers); the
+# values the sweeps store did not change: bench.py --dump-outputs at both commits, bit for bit, all five models
+# (profiles/hpow_edge_fix_outputs.txt).  The records in profiles/ that are stamped with the former tags no longer match.
 PARENT_TAGS = {
-    "hyperbolic": "064b6a7756ee17d54baf",
-    "doc": "fa09c748a97111ff4543",
-    "angular": "dccb688765a187effa5a",
-    "egno": "30b4f42837114a405473",
-    "d5": "5c9cb93da8d29f965a6f",
+    "hyperbolic": "25b693eda26925832dba",
+    "doc": "7527d626a66e2d73d15d",
+    "angular": "68e866bfaefd5c101062",
+    "egno": "a8ac75aff800c9874695",
+    "d5": "5c1570102f32c29a8c69",
 }
 
 
