@@ -426,6 +426,10 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* multi, int op, const double* p, 
  * Every output except `status` may be NULL.  The object `<artefact>.background` (CompilationArtifact.ensure_background()) is loaded on
  * first use and must carry the artefact's MODEL_TAG; INFLX_ERR_SYMBOL when it does not exist, INFLX_ERR_VERSION when it belongs to
  * another model.  Runs on the handle's stream; returns when the outputs are complete.
+ * The kernels write rows trajectory fastest; a transpose kernel (inflx_bg_rows_transpose) puts every pass of at most
+ * min(2^20, 2 GiB / (rows x 56 B)) trajectories into the layout above on the device, and two contiguous copies take it to `states`
+ * and `t`.  INFLX_EOM_HOST_SCATTER: the rows are copied out as the kernels wrote them and rearranged by the calling thread instead
+ * -- the same values, much slower; a call with rows >= 2341 (fewer than 2^14 trajectories per pass) always runs that way.
  */
 typedef enum inflx_eom_method {
   INFLX_EOM_RK4 = 0,
@@ -434,7 +438,8 @@ typedef enum inflx_eom_method {
 typedef enum inflx_eom_flags {
   INFLX_EOM_STOP_AT_END = 1,
   INFLX_EOM_FINAL_ONLY = 2,
-  INFLX_EOM_SAMPLE_T = 4    /* inflx_solve_eom_sampled: the samples are times, not e-fold counts */
+  INFLX_EOM_SAMPLE_T = 4,   /* inflx_solve_eom_sampled: the samples are times, not e-fold counts */
+  INFLX_EOM_HOST_SCATTER = 8 /* inflx_solve_eom: rearrange the rows on the host, not with the transpose kernel */
 } inflx_eom_flags;
 typedef enum inflx_eom_status {
   INFLX_EOM_COMPLETE = 0,   /* every requested step was taken */
@@ -447,6 +452,18 @@ typedef enum inflx_eom_status {
 int inflx_solve_eom(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps,
                     int method, double max_err, double dt, unsigned flags, double* states, double* t, double* efolds, int8_t* status,
                     int64_t* last_row);
+
+/*
+ * inflx_solve_eom with a device-resident result: `d_states` (B, rows, 6) and `d_t` (B, rows) are device pointers of
+ * `d_states_bytes` and `d_t_bytes` bytes (INFLX_ERR_SHAPE when one is too small for B x rows; either pointer may be NULL).  Every
+ * window of rows is transposed straight into them on the device: no row crosses to the host.  `efolds`, `status` and `last_row` are
+ * host arrays as for inflx_solve_eom.  INFLX_EOM_STOP_AT_END is the only flag (INFLX_EOM_FINAL_ONLY is INFLX_ERR_ARG: that mode
+ * keeps no rows).  Everything runs on `stream` (a hipStream_t; NULL: the handle's stream), and the call returns after it has
+ * synchronised that stream: the device arrays are complete on return, and work enqueued on `stream` afterwards sees them.
+ */
+int inflx_solve_eom_device(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows,
+                           size_t substeps, int method, double max_err, double dt, unsigned flags, double* d_states, size_t d_states_bytes,
+                           double* d_t, size_t d_t_bytes, double* efolds, int8_t* status, int64_t* last_row, void* stream);
 
 /*
  * The state of B trajectories where each has made `target[l]` e-folds: inflx_solve_eom's final-only run with one more way for a lane

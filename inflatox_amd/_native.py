@@ -32,7 +32,7 @@ LAYOUT_AOS, LAYOUT_SOA = 0, 1
 SWEEP_DEFAULT, SWEEP_FORCE_TILE = 0, 1  # inflx_sweep_flags
 TIME_BACK_TO_BACK, TIME_DOMINANT_ONLY, TIME_IN_PIPELINE, TIME_SINGLE_CALL = range(4)  # inflx_timing
 EOM_RK4, EOM_RKF = 0, 1  # inflx_eom_method
-EOM_STOP_AT_END, EOM_FINAL_ONLY, EOM_SAMPLE_T = 1, 2, 4  # inflx_eom_flags
+EOM_STOP_AT_END, EOM_FINAL_ONLY, EOM_SAMPLE_T, EOM_HOST_SCATTER = 1, 2, 4, 8  # inflx_eom_flags
 GATHER_PEER_PUSH, GATHER_RCCL = 0, 1  # inflx_gather: the exchange step of inflx_sweep_allgather_multi_ex
 
 _DP = C.POINTER(C.c_double)
@@ -105,6 +105,11 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, C.POINTER(C.c_int8), C.POINTER(C.c_int64)],
     ),
+    "inflx_solve_eom_device": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, C.c_void_p, _SIZE, C.c_void_p, _SIZE, _DP, C.POINTER(C.c_int8),
+         C.POINTER(C.c_int64), C.c_void_p],
+    ),
     "inflx_solve_eom_to_efolds": (
         C.c_int,
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, _DP, C.POINTER(C.c_int8)],
@@ -127,7 +132,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -454,6 +459,29 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return states, t, efolds, status, last_row
+
+    def solve_eom_device(self, p, init, rows: int, substeps: int, method: int, max_err: float, dt: float, flags: int, d_states_ptr: int, d_states_bytes: int,
+                         d_t_ptr: int, d_t_bytes: int, stream: int = 0):  # fmt: skip
+        """``solve_eom`` with the rows left on the device (include/inflx_hip.h: inflx_solve_eom_device): states (B, rows, 6) go to the
+        device address ``d_states_ptr`` and t (B, rows) to ``d_t_ptr`` (0: not wanted), buffers of the given byte sizes, on ``stream``
+        (a hipStream_t as an integer; 0: the handle's stream), which the call synchronises before it returns.  Returns (efolds,
+        status (int8), last_row (int64)), host arrays of shape (B,).  ``flags``: ``EOM_STOP_AT_END`` or 0."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        B = init.shape[0]
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        efolds = np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        last_row = np.empty(B, dtype=np.int64)
+        _check(
+            self._lib.inflx_solve_eom_device(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(rows), int(substeps), int(method), float(max_err), float(dt), int(flags),
+                C.c_void_p(d_states_ptr), int(d_states_bytes), C.c_void_p(d_t_ptr), int(d_t_bytes), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+                last_row.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(stream),
+            )
+        )  # fmt: skip
+        return efolds, status, last_row
 
     def solve_eom_to_efolds(self, p, init, target, max_steps: int, method: int, max_err: float, dt: float, flags: int):
         """B trajectories from ``init`` (B,4), each until its e-fold count reaches ``target`` (B,) (include/inflx_hip.h:

@@ -7,6 +7,7 @@ counterpart of a consistency map from ``GeneralisedAL.complete_analysis`` over t
 state at which a trajectory has made a given number of e-folds, and ``horizon_exit_map`` the state N_star e-folds before the end
 of inflation from every grid point: the (phi, chi, H) at which ``complete_analysis_ot`` and ``calc_V_array`` are evaluated.
 ``solve_eom_sampled`` returns every trajectory's state at one list of e-fold counts (or times) shared by all of them.
+``solve_eom_batch_device`` is ``solve_eom_batch`` with the trajectories left on the GPU as ``torch`` tensors.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -30,7 +31,7 @@ from . import _native
 from ._native import InflatoxShapeError
 from .compiler import CompilationArtifact
 
-__all__ = ["solve_eom", "solve_eom_batch", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
+__all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
            "SampledSolution", "STATUS"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
@@ -52,7 +53,8 @@ _METHODS = {"rk4": _native.EOM_RK4, "rkf": _native.EOM_RKF}
 class EoMSolution(NamedTuple):
     """What :func:`solve_eom_batch` returns.  ``states`` (B, steps, 5): phi^0, phi^1, chi^0, chi^1, H (a strided view); ``t`` and
     ``N`` (B, steps): cosmic time and e-folds of every row; ``status`` (B,) int8: ``STATUS`` codes; ``last_row`` (B,): the last row
-    that holds a state -- the rows after it are NaN; ``N_end`` (B,): N at epsilon_H = 1 with ``stop_at_end``, NaN otherwise."""
+    that holds a state -- the rows after it are NaN; ``N_end`` (B,): N at epsilon_H = 1 with ``stop_at_end``, NaN otherwise.
+    From :func:`solve_eom_batch_device`, ``states``, ``t`` and ``N`` are torch tensors on the GPU instead."""
 
     states: np.ndarray
     t: np.ndarray
@@ -139,6 +141,17 @@ def _pars(artifact, pars, B):
     return p
 
 
+def _check_batch(artifact, pars, steps, fields_init, derivatives_init, max_err, solver, dt, substeps):
+    """The argument checks of ``solve_eom_batch`` and ``solve_eom_batch_device``: (steps, substeps, max_err, dt, p, init (B, 4))."""
+    steps, substeps, max_err, dt = _check_common(artifact, steps, max_err, solver, dt, substeps)
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    p = _pars(artifact, pars, x.shape[0])
+    return steps, substeps, max_err, dt, p, np.concatenate([x, v], axis=1)
+
+
 def solve_eom_batch(artifact: CompilationArtifact, pars, steps: int, fields_init, derivatives_init, max_err: float = 1e-6, solver: str = "rkf", *,
                     dt: float | None = None, substeps: int = 1, stop_at_end: bool = False) -> EoMSolution:  # fmt: skip
     """B trajectories at once, one GPU lane each.  ``fields_init`` and ``derivatives_init`` are (B, 2); ``pars`` is (n_par,),
@@ -150,16 +163,43 @@ def solve_eom_batch(artifact: CompilationArtifact, pars, steps: int, fields_init
     its accuracy); a trajectory that starts with epsilon_H >= 1 ends at once, with ``N_end`` = 0 and row 0 its last row.  A trajectory
     that stops for another reason (``status``) has NaN rows from there on.  However large ``substeps``, no kernel launch takes more
     than 256 accepted steps per trajectory (a row may span launches).  Bad arguments raise before anything runs on the device."""
-    steps, substeps, max_err, dt = _check_common(artifact, steps, max_err, solver, dt, substeps)
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
-    B = x.shape[0]
-    p = _pars(artifact, pars, B)
-    init = np.concatenate([x, v], axis=1)
+    steps, substeps, max_err, dt, p, init = _check_batch(artifact, pars, steps, fields_init, derivatives_init, max_err, solver, dt, substeps)
     flags = _native.EOM_STOP_AT_END if stop_at_end else 0
     states, t, n_end, status, last_row = _dylib(artifact).solve_eom(p, init, steps, substeps, _METHODS[solver], max_err, dt or 0.0, flags)
+    return EoMSolution(states[:, :, :5], t, states[:, :, 5], status, last_row, n_end)
+
+
+def solve_eom_batch_device(artifact: CompilationArtifact, pars, steps: int, fields_init, derivatives_init, max_err: float = 1e-6, solver: str = "rkf", *,
+                           dt: float | None = None, substeps: int = 1, stop_at_end: bool = False) -> EoMSolution:  # fmt: skip
+    """``solve_eom_batch`` with a DEVICE-RESIDENT result: the same arguments, checked in the same order before torch or the device is
+    touched, and the same values bit for bit.  ``states`` (B, steps, 5), ``t`` and ``N`` (B, steps) are ``torch.float64`` tensors on
+    the GPU of the artefact's handle -- views of one (B, steps, 6) and one (B, steps) tensor, written there by the transpose kernel:
+    no row crosses PCIe.  They speak DLPack (``__dlpack__``) and ``__cuda_array_interface__``, so CuPy / JAX / numba consumers take
+    them without a copy.  ``status``, ``last_row`` and ``N_end`` are numpy arrays as in ``solve_eom_batch``.  As for
+    ``GeneralisedAL.complete_analysis_device``, the run is ordered after what torch's current stream has enqueued and torch's current
+    stream is ordered after the run: the tensors can be used like the result of any torch operation."""
+    steps, substeps, max_err, dt, p, init = _check_batch(artifact, pars, steps, fields_init, derivatives_init, max_err, solver, dt, substeps)
+    flags = _native.EOM_STOP_AT_END if stop_at_end else 0
+    import torch
+
+    lib = _dylib(artifact)
+    B = init.shape[0]
+    device = torch.device("cuda", lib.device)
+    if getattr(artifact, "_background_torch_stream", None) is None:
+        artifact._background_torch_stream = torch.cuda.Stream(device=device)
+    side = artifact._background_torch_stream
+    states = torch.empty((B, steps, 6), dtype=torch.float64, device=device)
+    t = torch.empty((B, steps), dtype=torch.float64, device=device)
+    if B:
+        consumer = torch.cuda.current_stream(device)
+        side.wait_stream(consumer)  # the tensors were allocated on the consumer's stream
+        n_end, status, last_row = lib.solve_eom_device(p, init, steps, substeps, _METHODS[solver], max_err, dt or 0.0, flags, states.data_ptr(),
+                                                       states.numel() * 8, t.data_ptr(), t.numel() * 8, stream=side.cuda_stream)  # fmt: skip
+        consumer.wait_stream(side)
+        states.record_stream(side)
+        t.record_stream(side)
+    else:
+        n_end, status, last_row = np.empty(0), np.empty(0, dtype=np.int8), np.empty(0, dtype=np.int64)
     return EoMSolution(states[:, :, :5], t, states[:, :, 5], status, last_row, n_end)
 
 

@@ -398,7 +398,7 @@ def _build_code_object(header_text: str, options: list[str], tag: str, groups: i
     return cached, log, code
 
 
-_BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "inflx_background_abi.h")
+_BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "inflx_background_abi.h", "inflx_background_rows.h")
 
 
 def _build_background_object(header_text: str, eom_text: str, options: list[str], tag: str):

@@ -1,5 +1,5 @@
 // Layout shared by libinflx_hip.so (csrc/inflx_hip.cpp, inflx_solve_eom) and the background kernels
-// (csrc/inflx_background_kernels.hip): the kernels' argument block and the carry planes.  Both sides include this header; the
+// (csrc/inflx_background_kernels.hip): the kernels' argument blocks and the carry planes.  Both sides include this header; the
 // background object exports INFLX_BG_ABI, and the host refuses an object whose value differs from its own.
 #pragma once
 #include <stddef.h>
@@ -7,7 +7,7 @@
 
 // (overridable with -DINFLX_BG_ABI_VERSION=<n> so that a test can build an object of another layout version and see it refused)
 #ifndef INFLX_BG_ABI_VERSION
-#define INFLX_BG_ABI_VERSION 4
+#define INFLX_BG_ABI_VERSION 5
 #endif
 // the artefact ABI major a background object reports by default: the core object's (csrc/inflx_sweep_kernels.hip, overridable there
 // and here with -DINFLX_ABI_VERSION_MAJOR, which the background object is built with whenever the core object is)
@@ -62,3 +62,23 @@ static_assert(offsetof(InflxBgArgs, step_begin) == 48 && offsetof(InflxBgArgs, s
 
 // bound of one launch: accepted steps per lane (each of at most 50 trials)
 #define INFLX_BG_STEPS_PER_LAUNCH 256u
+
+// Argument block of inflx_bg_rows_transpose (csrc/inflx_background_rows.h): one window of row planes -- the slots [0, filled) of
+// `rows`, which hold the rows [row_base, row_base + filled) of n lanes -- into the trajectory-major arrays of inflx_solve_eom:
+//   out_y[((lane_off + lane) * rows_total + row) * 6 + c], c = 0..5        out_t[(lane_off + lane) * rows_total + row]
+// Nothing else of out_y / out_t is written; either may be NULL.
+struct InflxBgRowsArgs {
+  const double* rows;   // [slot][7][n]: y[0..5], t
+  double* out_y;        // (lanes, rows_total, 6) -- or NULL
+  double* out_t;        // (lanes, rows_total) -- or NULL
+  uint64_t n;           // lanes of the planes
+  uint64_t lane_off;    // trajectory of lane 0 in out_y / out_t
+  uint64_t rows_total;  // rows per trajectory in out_y / out_t
+  uint64_t row_base;    // row held by slot 0
+  uint64_t filled;      // slots of the window
+};
+static_assert(sizeof(InflxBgRowsArgs) == 64, "InflxBgRowsArgs layout");
+static_assert(offsetof(InflxBgRowsArgs, out_y) == 8 && offsetof(InflxBgRowsArgs, out_t) == 16 && offsetof(InflxBgRowsArgs, n) == 24 &&
+                  offsetof(InflxBgRowsArgs, lane_off) == 32 && offsetof(InflxBgRowsArgs, rows_total) == 40 &&
+                  offsetof(InflxBgRowsArgs, row_base) == 48 && offsetof(InflxBgRowsArgs, filled) == 56,
+              "InflxBgRowsArgs layout");

@@ -14,6 +14,8 @@
 // (inflx_bg_step_target), and that state -- with epsilon_H there -- is what its carry holds.  The *_sampled kernels (final-only)
 // emit the state at every point of a list of e-fold counts or times shared by all lanes (inflx_bg_step_sampled) into planes
 // [sample][8][n]: y[0..5], t, epsilon_H.
+// inflx_bg_rows_transpose, which knows nothing of the model, copies a window of row planes into the trajectory-major arrays
+// inflx_solve_eom hands out (csrc/inflx_background_rows.h); it lives here because this is the object inflx_solve_eom loads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,6 +36,7 @@
 static_assert(INFLX_DIM == 2, "the background kernels need a two-field model");
 
 #include "inflx_background_abi.h"
+#include "inflx_background_rows.h"
 
 #define INFLX_EXPORT extern "C" __device__ __attribute__((used, visibility("default")))
 #ifndef INFLX_ABI_VERSION_MAJOR
@@ -234,3 +237,12 @@ __device__ __forceinline__ void advance_samples(const InflxBgArgs& a) {
 }
 extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_advance_rk4_sampled(const InflxBgArgs a) { advance_samples<INFLX_BG_RK4>(a); }
 extern "C" __global__ __launch_bounds__(kBgThreads) void inflx_bg_advance_rkf_sampled(const InflxBgArgs a) { advance_samples<INFLX_BG_RKF>(a); }
+
+// One tile of 64 lanes x 8 slots per workgroup, through LDS: planes [slot][7][n] -> out_y (lanes, rows_total, 6), out_t (lanes,
+// rows_total).  Grid: inflx_bg_rows_blocks(n, filled) workgroups.  Both phases: csrc/inflx_background_rows.h.
+extern "C" __global__ __launch_bounds__(INFLX_BG_ROWS_THREADS) void inflx_bg_rows_transpose(const InflxBgRowsArgs a) {
+  __shared__ double tile[INFLX_BG_ROWS_TILE_DOUBLES];
+  inflx_bg_rows_load(a, blockIdx.x, threadIdx.x, tile);
+  __syncthreads();
+  inflx_bg_rows_store(a, blockIdx.x, threadIdx.x, tile);
+}

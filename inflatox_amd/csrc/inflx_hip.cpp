@@ -38,6 +38,7 @@
 #include <unistd.h>
 
 #include "inflx_background_abi.h"
+#include "inflx_background_rows.h"
 #include "inflx_kernel_abi.h"
 
 namespace {
@@ -420,6 +421,7 @@ struct inflx_model {
   hipFunction_t bg_advance[2][2] = {};  // [method][store rows]
   hipFunction_t bg_target[2] = {};      // [method]: final-only with a target on N (inflx_solve_eom_to_efolds)
   hipFunction_t bg_sampled[2] = {};     // [method]: final-only with a list of samples (inflx_solve_eom_sampled)
+  hipFunction_t bg_rows_transpose = nullptr;  // row planes -> (lanes, rows, 6) and (lanes, rows) (csrc/inflx_background_rows.h)
 };
 
 namespace {
@@ -2744,9 +2746,7 @@ namespace {
 
 // the kernels' argument block and the carry planes: csrc/inflx_background_abi.h
 static_assert(kAbiMajor == INFLX_BG_DEFAULT_ABI_MAJOR, "a background object reports the core object's ABI major: change both together");
-// bounds of one call's passes: lanes per chunk, bytes of the device row buffer (the steps of one launch: INFLX_BG_STEPS_PER_LAUNCH)
-constexpr size_t kBgMaxLanes = size_t(1) << 20;
-constexpr size_t kBgRowBytes = size_t(256) << 20;
+// bounds of one call's passes (kBgMaxLanes, kBgRowBytes) and the plan of a row call's passes: csrc/inflx_background_rows.h
 
 // Load `<artefact>.background` beside the core object: it must carry the core object's MODEL_TAG.
 int need_background(inflx_model* m) {
@@ -2780,8 +2780,10 @@ int need_background(inflx_model* m) {
   const char* names[2][2] = {{"inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows"}, {"inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows"}};
   const char* target_names[2] = {"inflx_bg_advance_rk4_target", "inflx_bg_advance_rkf_target"};
   const char* sampled_names[2] = {"inflx_bg_advance_rk4_sampled", "inflx_bg_advance_rkf_sampled"};
-  hipFunction_t init = nullptr, adv[2][2] = {}, tgt[2] = {}, smp[2] = {};
+  hipFunction_t init = nullptr, adv[2][2] = {}, tgt[2] = {}, smp[2] = {}, transpose = nullptr;
   if (hipModuleGetFunction(&init, module, "inflx_bg_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_bg_init", path.c_str()));
+  if (hipModuleGetFunction(&transpose, module, "inflx_bg_rows_transpose") != hipSuccess)
+    return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_bg_rows_transpose", path.c_str()));
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b)
       if (hipModuleGetFunction(&adv[a][b], module, names[a][b]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a][b]));
@@ -2791,6 +2793,7 @@ int need_background(inflx_model* m) {
     if (hipModuleGetFunction(&smp[a], module, sampled_names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), sampled_names[a]));
   m->bg_module = module;
   m->bg_init = init;
+  m->bg_rows_transpose = transpose;
   for (int a = 0; a < 2; ++a) m->bg_target[a] = tgt[a];
   for (int a = 0; a < 2; ++a) m->bg_sampled[a] = smp[a];
   for (int a = 0; a < 2; ++a)
@@ -2802,43 +2805,49 @@ int need_background(inflx_model* m) {
 // device buffers of one call, released on every way out
 struct BgBuffers {
   double *p = nullptr, *init = nullptr, *carry = nullptr, *rows = nullptr, *target = nullptr, *samples = nullptr;
+  double *out_y = nullptr, *out_t = nullptr;  // a pass's whole result in the caller's layout (inflx_solve_eom's host result)
   uint32_t* running = nullptr;
   ~BgBuffers() {
-    for (double* d : {p, init, carry, rows, target, samples})
+    for (double* d : {p, init, carry, rows, target, samples, out_y, out_t})
       if (d) (void)hipFree(d);
     if (running) (void)hipFree(running);
   }
 };
 
-}  // namespace
 
-extern "C" {
-
-int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps, int method,
-                    double max_err, double dt, unsigned flags, double* states, double* t, double* efolds, int8_t* status, int64_t* last_row) {
-  INFLX_SERIALISE(m);
+// the argument checks inflx_solve_eom and inflx_solve_eom_device share, in inflx_solve_eom's order
+int check_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, size_t B, size_t rows, size_t substeps, int method, double max_err, double dt,
+                    unsigned flags, unsigned known_flags, const int8_t* status) {
   if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
   if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the background solver requires a 2-field model (model has %u fields)", m->dim);
   if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
   if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
   if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
   if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
-  if (flags & ~(unsigned)(INFLX_EOM_STOP_AT_END | INFLX_EOM_FINAL_ONLY)) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
+  if (flags & ~known_flags) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
   if (rows < 1) return fail(INFLX_ERR_ARG, "rows must be at least 1 (got %zu)", rows);
   if (substeps < 1 || substeps > 0xffffffffu) return fail(INFLX_ERR_ARG, "substeps must be in [1, 2^32) (got %zu)", substeps);
   if ((uint64_t)(rows - 1) > (UINT64_C(1) << 62) / substeps) return fail(INFLX_ERR_ARG, "rows x substeps exceeds 2^62 accepted steps");
   if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
   if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
   if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
-  if (B == 0) return INFLX_OK;
-  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
-  HIP_TRY(hipSetDevice(m->device));
-  int rc = need_background(m);
-  if (rc) return rc;
+  return INFLX_OK;
+}
+
+// The passes of inflx_solve_eom and inflx_solve_eom_device on stream `s`, arguments checked and the background object loaded.
+// `device_result`: `states` and `t` are the caller's device arrays and every window of rows is transposed straight into them.
+// Otherwise inflx_bg_rows_plan decides: the windows of a pass are transposed into a device array of the pass's whole result, which
+// two contiguous copies take to the host -- or (INFLX_EOM_HOST_SCATTER, rows >= 2341) every window is copied out as planes and
+// scattered by this thread.  Returns after `s` has been synchronised.
+int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps,
+                     int method, double max_err, double dt, unsigned flags, double* states, double* t, bool device_result, double* efolds, int8_t* status,
+                     int64_t* last_row) {
+  int rc;
   const bool final_only = (flags & INFLX_EOM_FINAL_ONLY) != 0;
   const bool store = !final_only && (states || t);
-  hipStream_t s = m->stream;
-  const size_t nc_max = std::min(B, kBgMaxLanes);
+  const InflxBgRowsPlan plan = inflx_bg_rows_plan(B, rows, (flags & INFLX_EOM_HOST_SCATTER) != 0, device_result);
+  const bool transposed = store && plan.transposed, staged = transposed && !device_result;
+  const size_t nc_max = store ? plan.lanes_per_pass : std::min(B, kBgMaxLanes);
   size_t cap_rows = 0;  // rows the device row buffer holds
   if (store) cap_rows = std::max<size_t>(2, std::min(rows, kBgRowBytes / (7 * sizeof(double) * nc_max)));
   const uint64_t total_steps = (uint64_t)(rows - 1) * substeps;  // accepted-step indices of the call (checked against overflow above)
@@ -2848,7 +2857,9 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
   if (store) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.rows), cap_rows * 7 * nc_max * sizeof(double)));
-  std::vector<double> host_rows(store ? cap_rows * 7 * nc_max : 0), host_carry(nc_max * INFLX_BG_CARRY_ROW_PLANES);
+  if (staged && states) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out_y), nc_max * rows * 6 * sizeof(double)));
+  if (staged && t) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out_t), nc_max * rows * sizeof(double)));
+  std::vector<double> host_rows(store && !transposed ? cap_rows * 7 * nc_max : 0), host_carry(nc_max * INFLX_BG_CARRY_ROW_PLANES);
   hipFunction_t advance = m->bg_advance[method == INFLX_EOM_RKF ? 1 : 0][store ? 1 : 0];
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
@@ -2871,9 +2882,28 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
     HIP_TRY(hipModuleLaunchKernel(m->bg_init, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
     // the device buffer holds rows [row_base, rows_done): rows_done = 1 + the rows completed by the steps taken so far
     uint64_t row_base = 0, rows_done = 1, step = 0;
+    // the window [row_base, rows_done) leaves the row buffer: through the transpose kernel, which the stream orders before the next
+    // launch that writes the buffer, or through the host
     auto drain = [&]() -> int {
       const size_t filled = (size_t)(rows_done - row_base);
       if (!store || !filled) return INFLX_OK;
+      if (transposed) {
+        InflxBgRowsArgs ta;
+        memset(&ta, 0, sizeof ta);
+        ta.rows = buf.rows;
+        ta.out_y = staged ? buf.out_y : states;
+        ta.out_t = staged ? buf.out_t : t;
+        ta.n = n;
+        ta.lane_off = staged ? 0 : c0;
+        ta.rows_total = rows;
+        ta.row_base = row_base;
+        ta.filled = filled;
+        void* tparams[] = {&ta};
+        // (at most 2^28 / 56 row cells in a window: the grid is far below 2^31 workgroups)
+        HIP_TRY(hipModuleLaunchKernel(m->bg_rows_transpose, (unsigned)inflx_bg_rows_blocks(n, filled), 1, 1, INFLX_BG_ROWS_THREADS, 1, 1, 0, s, tparams, nullptr));
+        row_base = rows_done;
+        return INFLX_OK;
+      }
       HIP_TRY(hipMemcpyAsync(host_rows.data(), buf.rows, filled * 7 * n * sizeof(double), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       for (size_t r = 0; r < filled; ++r) {
@@ -2910,6 +2940,8 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
       }
     }
     if (store && (rc = drain())) return rc;  // (rows == 1: the initial state only)
+    if (staged && states) HIP_TRY(hipMemcpyAsync(states + c0 * rows * 6, buf.out_y, n * rows * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (staged && t) HIP_TRY(hipMemcpyAsync(t + c0 * rows, buf.out_t, n * rows * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_ROW_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
@@ -2925,6 +2957,42 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
     }
   }
   return sf_verdict(m);
+}
+
+}  // namespace
+
+extern "C" {
+
+int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps, int method,
+                    double max_err, double dt, unsigned flags, double* states, double* t, double* efolds, int8_t* status, int64_t* last_row) {
+  INFLX_SERIALISE(m);
+  int rc = check_solve_eom(m, p, P, n_p, B, rows, substeps, method, max_err, dt, flags, INFLX_EOM_STOP_AT_END | INFLX_EOM_FINAL_ONLY | INFLX_EOM_HOST_SCATTER, status);
+  if (rc) return rc;
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_background(m))) return rc;
+  return solve_eom_passes(m, m->stream, p, P, n_p, init, B, rows, substeps, method, max_err, dt, flags, states, t, /*device_result=*/false, efolds, status, last_row);
+}
+
+int inflx_solve_eom_device(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t rows, size_t substeps, int method,
+                           double max_err, double dt, unsigned flags, double* d_states, size_t d_states_bytes, double* d_t, size_t d_t_bytes, double* efolds,
+                           int8_t* status, int64_t* last_row, void* stream) {
+  INFLX_SERIALISE(m);
+  if (flags & INFLX_EOM_FINAL_ONLY) return fail(INFLX_ERR_ARG, "INFLX_EOM_FINAL_ONLY has no device-resident form: its result is the carry, which inflx_solve_eom returns");
+  int rc = check_solve_eom(m, p, P, n_p, B, rows, substeps, method, max_err, dt, flags, INFLX_EOM_STOP_AT_END, status);
+  if (rc) return rc;
+  size_t cells = 0;  // B x rows
+  if (__builtin_mul_overflow(B, rows, &cells) || cells > SIZE_MAX / (6 * sizeof(double))) return fail(INFLX_ERR_SHAPE, "%zu trajectories x %zu rows exceed the address space", B, rows);
+  if (d_states && d_states_bytes < cells * 6 * sizeof(double))
+    return fail(INFLX_ERR_SHAPE, "states buffer has %zu bytes, the call writes %zu", d_states_bytes, cells * 6 * sizeof(double));
+  if (d_t && d_t_bytes < cells * sizeof(double)) return fail(INFLX_ERR_SHAPE, "t buffer has %zu bytes, the call writes %zu", d_t_bytes, cells * sizeof(double));
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_background(m))) return rc;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
+  return solve_eom_passes(m, s, p, P, n_p, init, B, rows, substeps, method, max_err, dt, flags, d_states, d_t, /*device_result=*/true, efolds, status, last_row);
 }
 
 int inflx_solve_eom_to_efolds(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* target, size_t max_steps,
