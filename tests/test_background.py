@@ -10,6 +10,7 @@ import pytest
 import sympy
 
 import workloads
+from background_truth import truth_functions
 from background_reference import (
     COMPLETE,
     ENDED,
@@ -50,8 +51,9 @@ def _points(name, n, seed=0):
 
 @pytest.mark.parametrize("name", MODELS)
 def test_generated_eom_matches_sympy(name):
-    """inflx_eom_point (compiled for the host) against sympy at 200 seeded points: eom^a, V and G_ab xd^a xd^b evaluated by lambdify
-    in 40-digit arithmetic are the truth; the generated code must be within four times the error of lambdify's own float64
+    """inflx_eom_point (compiled for the host) against sympy at 200 seeded points: eom^a, V and G_ab xd^a xd^b of an Euler-Lagrange
+    derivation that shares nothing with ``model.eom_fields`` (background_truth.euler_lagrange_eom), evaluated by lambdify in 40-digit
+    arithmetic, are the truth; the generated code must be within four times the error of lambdify's own float64
     evaluation of the same expressions, or 1e-12 of the value's scale.  The two float64 programs round differently (shared nodes,
     pow chains of up to x^12 with up to 11 half-ulps), and EGNO's eom^a cancel to ~1e-7 at some points in both (its expressions
     are sums of ~100 rational terms): what is asserted is that the staged code is as accurate as the expression allows."""
@@ -60,13 +62,13 @@ def test_generated_eom_matches_sympy(name):
     spec, art = workloads.artifact_for(name)
     twin = BackgroundTwin(art)
     model = workloads.model_for(name)
-    exact_fn = model_functions(model, art.symbol_dictionary, modules=("mpmath",))
+    exact_fn = truth_functions(model, art.symbol_dictionary, modules="mpmath")
     float_fn = model_functions(model, art.symbol_dictionary)
     pts = _points(name, 200)
     got = twin.eom(spec.args, pts)
     with mpmath.workdps(40):
         mp_args = [mpmath.mpf(float(v)) for v in spec.args]
-        exact = np.array([exact_fn(*[mpmath.mpf(float(v)) for v in pt], mp_args) for pt in pts])
+        exact = np.array([[float(v) for v in exact_fn(*[mpmath.mpf(float(v)) for v in pt], mp_args)] for pt in pts])
     plain = np.array([float_fn(*pt, spec.args) for pt in pts])
     assert np.all(np.isfinite(got)) and np.all(np.isfinite(exact))
     scale = np.maximum(np.abs(exact), np.max(np.abs(exact), axis=0) * 1e-3)
