@@ -41,5 +41,10 @@ unsigned sf_status_take() {
   inflx_sf_status_host = 0u;
   return v;
 }
+// whether 2F0 answers (a, b, x) from its asymptotic series (the seam the edge tests look for by bisection)
+int sf_2F0_asymptotic_accepts(double a, double b, double x) {
+  double v;
+  return inflx_sf_hyperg_2F0_asymptotic(a, b, x, &v) ? 1 : 0;
+}
 void sf_0F1(double c, const double* x, int n, double* out) { for (int i = 0; i < n; ++i) out[i] = inflx_sf_hyperg_0F1(c, x[i]); }
 }
