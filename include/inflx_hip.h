@@ -508,6 +508,44 @@ int inflx_solve_eom_sampled(inflx_model* model, const double* p, size_t P, size_
                             size_t S, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds,
                             int8_t* status, uint32_t* n_stored);
 
+/*
+ * Trajectory kinematics at n states (csrc/inflx_kinematics.h): a post-pass over states of the background solver -- rows of
+ * inflx_solve_eom, states of inflx_solve_eom_to_efolds or inflx_solve_eom_sampled -- or over any other states.  With kin =
+ * G_ab chi^a chi^b, vchi = d_a V chi^a and cross = (d_0 V chi_1 - d_1 V chi_0) / sqrt(det G), chi_a = G_ab chi^b:
+ *   plane 0  eps_H     = kin / 2 / H^2, bit for bit the solver's own epsilon_H at that state
+ *   plane 1  eta_par   = 3 + vchi / (H kin) = -sigma_ddot / (H sigma_dot)
+ *   plane 2  omega     = cross / (kin H): the turn rate per e-fold Omega / H, SIGNED (> 0: the trajectory turns counter-clockwise in the
+ *                        (phi^0, phi^1) chart); the sweeps' omega >= 0 corresponds to its absolute value
+ *   plane 3  sigma_dot = sqrt(kin)
+ *   plane 4  V_sigma   = vchi / sigma_dot, the gradient along the velocity
+ *   plane 5  V_N       = cross / sigma_dot, the gradient normal to it; V_sigma^2 + V_N^2 = |dV|^2
+ * IEEE arithmetic throughout.  A component of a state that is not finite (NaN, +-inf) gives six NaNs there, whether or not the model
+ * depends on that component (0 * y[c], summed over the five, is added to every plane); a state at rest (kin = 0) gives eps_H = 0, sigma_dot = 0
+ * and NaN in the other four.
+ *   p          (P, n_p) parameter rows, P = 1 (shared) or n / traj_len: one per run of traj_len consecutive states
+ *   states     state i is states[i * ld + c], c = 0..4 = phi^0, phi^1, chi^0, chi^1, H; ld >= 5 (6 for the rows of inflx_solve_eom, whose
+ *              sixth column is not read).  The array holds (n - 1) * ld + 5 doubles at least.
+ *   traj_len   >= 1 and a divisor of n
+ *   out        (6, n): the planes above
+ * The object `<artefact>.kinematics` (CompilationArtifact.ensure_kinematics()) is loaded on first use and must carry the artefact's
+ * MODEL_TAG and this library's layout word INFLX_KIN_ABI; INFLX_ERR_SYMBOL when it does not exist, INFLX_ERR_VERSION when it belongs
+ * to another model or layout.  It is independent of `<artefact>.background`.  Arguments are checked before anything touches the
+ * device; n = 0 succeeds and launches nothing.  Runs on the handle's stream in chunks of at most 2^20 states -- each copied in,
+ * evaluated and its six plane segments copied out -- and returns when `out` is complete.  A USE_GSL artefact follows the error
+ * policy of inflx_solve_eom (inflx_sf_policy).
+ */
+int inflx_kinematics(inflx_model* model, const double* p, size_t P, size_t n_p, const double* states, size_t n, size_t ld, size_t traj_len,
+                     double* out);
+
+/*
+ * inflx_kinematics on device arrays: `d_states` (d_states_bytes >= ((n - 1) * ld + 5) * 8) and `d_out` (d_out_bytes >= 6 * n * 8) are
+ * device pointers, INFLX_ERR_SHAPE when a buffer is too small; `p` is a host array.  One launch on `stream` (a hipStream_t; NULL: the
+ * handle's stream); like inflx_solve_eom_device the call returns after it has synchronised that stream: `d_out` is complete on
+ * return, and work enqueued on `stream` afterwards sees it.  No state and no result crosses to the host.
+ */
+int inflx_kinematics_device(inflx_model* model, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n,
+                            size_t ld, size_t traj_len, void* d_out, size_t d_out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,8 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, C.POINTER(C.c_int8), C.POINTER(C.c_uint32)],
     ),
+    "inflx_kinematics": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, _DP]),
+    "inflx_kinematics_device": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, C.c_void_p, _SIZE, _SIZE, _SIZE, _SIZE, C.c_void_p, _SIZE, C.c_void_p]),
 }
 
 
@@ -132,7 +134,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -529,6 +531,34 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return out, efolds, status, n_stored
+
+    # ---- trajectory kinematics (include/inflx_hip.h: inflx_kinematics) --------------------------
+    def kinematics(self, p, states: np.ndarray, n: int, ld: int, traj_len: int = 1) -> np.ndarray:
+        """The six kinematic quantities at ``n`` states ``ld`` doubles apart, the first at the first element of the float64 array
+        ``states`` (a view whose leading axes advance uniformly by ``ld``): phi^0, phi^1, chi^0, chi^1, H each; ``p`` is (n_par,) or
+        (n / traj_len, n_par), one row per run of ``traj_len`` states.  Returns (6, n): eps_H, eta_par, omega, sigma_dot, V_sigma,
+        V_N.  The kinematics object must be in place (``CompilationArtifact.ensure_kinematics``); arguments are checked by the
+        caller (inflatox_amd.background) and again by the library."""
+        p = _f64(p, "p")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((6, n))
+        _check(self._lib.inflx_kinematics(self._h, _ptr(p), P, self.n_parameters, _ptr(states), int(n), int(ld), int(traj_len), _ptr(out)))
+        return out
+
+    def kinematics_device(self, p, d_states_ptr: int, d_states_bytes: int, n: int, ld: int, traj_len: int, d_out_ptr: int, d_out_bytes: int, stream: int = 0) -> None:
+        """``kinematics`` on device arrays (include/inflx_hip.h: inflx_kinematics_device): n states of stride ``ld`` doubles at the
+        device address ``d_states_ptr``, the planes (6, n) to ``d_out_ptr``, buffers of the given byte sizes, on ``stream`` (a
+        hipStream_t as an integer; 0: the handle's stream), which the call synchronises before it returns."""
+        p = _f64(p, "p")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        _check(
+            self._lib.inflx_kinematics_device(
+                self._h, _ptr(p), P, self.n_parameters, C.c_void_p(d_states_ptr), int(d_states_bytes), int(n), int(ld), int(traj_len), C.c_void_p(d_out_ptr),
+                int(d_out_bytes), C.c_void_p(stream),
+            )
+        )  # fmt: skip
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

@@ -8,6 +8,10 @@ state at which a trajectory has made a given number of e-folds, and ``horizon_ex
 of inflation from every grid point: the (phi, chi, H) at which ``complete_analysis_ot`` and ``calc_V_array`` are evaluated.
 ``solve_eom_sampled`` returns every trajectory's state at one list of e-fold counts (or times) shared by all of them.
 ``solve_eom_batch_device`` is ``solve_eom_batch`` with the trajectories left on the GPU as ``torch`` tensors.
+``kinematics`` evaluates epsilon_H, eta_parallel, the turn rate per e-fold and the gradient along and across the velocity at any of
+these states -- host arrays, or the device-resident rows of ``solve_eom_batch_device`` without a byte crossing PCIe -- and
+``turn_rate_map`` is ``horizon_exit_map`` followed by ``kinematics``: the measured counterpart, over the same grid, of what
+``GeneralisedAL.complete_analysis`` predicts from the potential alone.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -32,7 +36,7 @@ from ._native import InflatoxShapeError
 from .compiler import CompilationArtifact
 
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
-           "SampledSolution", "STATUS"]  # fmt: skip
+           "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -93,9 +97,11 @@ class SampledSolution(NamedTuple):
     status: np.ndarray
 
 
-def _dylib(artifact: CompilationArtifact) -> _native.InflatoxDevLib:
-    """The artefact's background object (built on first use) and one handle per artefact, opened on device 0 without the basis check."""
-    artifact.ensure_background()
+def _dylib(artifact: CompilationArtifact, background: bool = True) -> _native.InflatoxDevLib:
+    """The artefact's background object (built on first use; ``kinematics`` does without it) and one handle per artefact, opened on
+    device 0 without the basis check."""
+    if background:
+        artifact.ensure_background()
     lib = getattr(artifact, "_background_dylib", None)
     if lib is None:
         lib = _native.InflatoxDevLib(artifact.shared_object_path)
@@ -372,3 +378,127 @@ def horizon_exit_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N
     state = state.reshape(N0, N1, 5)
     status = status.reshape(N0, N1)
     return (state, n_end, status) if return_status else (state, n_end)
+
+
+class Kinematics(NamedTuple):
+    """What :func:`kinematics` returns, each member of the shape of the states' leading axes and all six views of one (6, ...)
+    array.  With sigma_dot^2 = G_ab chi^a chi^b: ``eps_H`` = sigma_dot^2 / (2 H^2), bit for bit the solver's own epsilon_H;
+    ``eta_par`` = -sigma_ddot / (H sigma_dot); ``omega`` = Omega / H, the turn rate per e-fold, SIGNED (positive: the trajectory
+    turns counter-clockwise in the (phi^0, phi^1) chart) -- the omega >= 0 of ``GeneralisedAL.complete_analysis`` corresponds to
+    its absolute value; ``sigma_dot``; ``V_sigma`` and ``V_N``, the gradient of the potential along the velocity and normal to it
+    (V_sigma^2 + V_N^2 = |dV|^2)."""
+
+    eps_H: np.ndarray
+    eta_par: np.ndarray
+    omega: np.ndarray
+    sigma_dot: np.ndarray
+    V_sigma: np.ndarray
+    V_N: np.ndarray
+
+
+#: the host path reads a strided array in place only up to this many doubles between states: the whole span is uploaded, and beyond
+#: the solver's rows (6) and a little slack a contiguous copy of 40 bytes per state is cheaper than the gaps (``sol.states[:, 0]``
+#: of (B, steps, 6) rows has 6 * steps doubles between states).  A device tensor is read in place at any uniform stride.
+_HOST_MAX_LD = 8
+
+
+def _state_stride(shape, strides):
+    """The distance ``ld``, in elements, between consecutive states of an array of states (..., 5) with ``strides`` in elements, when
+    there is one: the last stride is 1 and the leading axes advance uniformly, as in a C-contiguous array (ld = 5) or in the first
+    five columns of the solver's (B, steps, 6) rows (ld = 6).  None: the array has to be made contiguous."""
+    if strides[-1] != 1:
+        return None
+    ld = None
+    inner = 1  # states one step of the next axis to the left spans
+    for size, stride in zip(reversed(shape[:-1]), reversed(strides[:-1])):
+        if size > 1:
+            if stride <= 0 or stride % inner or (ld is not None and stride != ld * inner):
+                return None
+            ld = stride // inner
+        inner *= size
+    if ld is None:
+        return 5
+    return ld if ld >= 5 else None
+
+
+def kinematics(artifact: CompilationArtifact, pars, states) -> Kinematics:
+    """epsilon_H, eta_parallel, the turn rate and the slopes of the potential at ``states``: (5,), (n, 5) or (B, S, 5) with the
+    components phi^0, phi^1, chi^0, chi^1, H -- ``EoMSolution.states``, ``EfoldsState.state``, ``SampledSolution.states``, the
+    ``state`` of ``horizon_exit_map`` or states from anywhere else.  ``pars`` is (n_par,), or one row per leading index: (n, n_par)
+    for (n, 5) states, (B, n_par) for (B, S, 5) states.  A pointwise pass of one GPU lane per state (csrc/inflx_kinematics.h); the
+    kernel is built into ``<artefact>.kinematics`` on first use (``CompilationArtifact.ensure_kinematics``) and the integrator is
+    not involved.  A component that is not finite (NaN, +-inf) gives six NaNs, whether or not the model depends on that component --
+    the NaN rows after a trajectory stopped stay NaN --, a state at rest
+    (sigma_dot = 0) has eps_H = 0, sigma_dot = 0 and NaN elsewhere.
+
+    A numpy array (or anything ``numpy.asarray`` takes) is evaluated in chunks of at most 2^20 states and returns numpy arrays; a
+    view with a uniform stride of at most 8 doubles between states, such as ``EoMSolution.states``, is read in place, any other
+    is made contiguous first.  A ``torch.float64`` tensor on the GPU takes the
+    device path: no byte crosses PCIe and the result is torch tensors, ordered with torch's current stream the way
+    ``solve_eom_batch_device`` orders its result.  A tensor whose last stride is 1 and whose row stride is uniform --
+    ``solve_eom_batch_device(...).states``, a view of the (B, steps, 6) rows -- is read in place, any other is made contiguous
+    first.  Bad arguments raise ``InflatoxShapeError`` / ``ValueError`` before the device is touched."""
+    if getattr(artifact, "n_fields", None) != 2:
+        raise InflatoxShapeError(f"the kinematics require a 2-field model (model has {getattr(artifact, 'n_fields', None)} fields)")
+    on_device = type(states).__module__.split(".")[0] == "torch" and bool(getattr(states, "is_cuda", False))
+    if on_device:
+        import torch
+
+        if states.dtype != torch.float64:
+            raise ValueError(f"a device tensor of states must be torch.float64 (got {states.dtype})")
+        if (states.device.index or 0) != 0:
+            raise ValueError(f"the artefact's handle is on device 0; the states are on {states.device}")
+        y = states.detach()
+    else:
+        try:
+            y = np.asarray(states, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("states must be convertible to a float64 array") from None
+    shape = tuple(y.shape)
+    if len(shape) not in (1, 2, 3) or shape[-1] != 5:
+        raise InflatoxShapeError(f"states must have shape (5,), (n, 5) or (B, S, 5) (got {shape})")
+    lead = shape[:-1]
+    n = int(np.prod(lead, dtype=np.int64))
+    traj_len = shape[1] if len(shape) == 3 else 1
+    p = _pars(artifact, pars, lead[0] if lead else 1)
+    if on_device:
+        out = torch.empty((6, n), dtype=torch.float64, device=y.device)
+        if n:
+            ld = _state_stride(shape, tuple(y.stride()))
+            if ld is None:
+                y, ld = y.contiguous(), 5
+            lib = _dylib(artifact, background=False)
+            artifact.ensure_kinematics()
+            if getattr(artifact, "_background_torch_stream", None) is None:
+                artifact._background_torch_stream = torch.cuda.Stream(device=y.device)
+            side = artifact._background_torch_stream
+            consumer = torch.cuda.current_stream(y.device)
+            side.wait_stream(consumer)  # the states were written, and `out` allocated, on the consumer's stream
+            held = y.untyped_storage().nbytes() - y.storage_offset() * 8  # what the tensor's storage holds from its first element on
+            lib.kinematics_device(p, y.data_ptr(), held, n, ld, traj_len, out.data_ptr(), out.numel() * 8, stream=side.cuda_stream)
+            consumer.wait_stream(side)
+            y.record_stream(side)
+            out.record_stream(side)
+        return Kinematics(*out.reshape((6, *lead)))
+    if n == 0:
+        return Kinematics(*np.empty((6, *lead)))
+    ld = _state_stride(shape, tuple(st // 8 if st % 8 == 0 else 0 for st in y.strides))
+    if ld is None or ld > _HOST_MAX_LD:
+        y, ld = np.ascontiguousarray(y), 5
+    lib = _dylib(artifact, background=False)
+    artifact.ensure_kinematics()
+    out = lib.kinematics(p, y, n, ld, traj_len)
+    return Kinematics(*out.reshape((6, *lead)))
+
+
+def turn_rate_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, derivatives_init=(0.0, 0.0),
+                  max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """``horizon_exit_map`` (same arguments) followed by ``kinematics`` at the exit states: ``(kin, state, N_end)`` with ``kin`` the
+    :class:`Kinematics` of (N0, N1) arrays at the state ``N_star`` e-folds before the end of inflation from every grid point, and
+    ``state`` (N0, N1, 5) and ``N_end`` (N0, N1) exactly ``horizon_exit_map``'s; ``return_status=True`` adds its (N0, N1) status map.
+    All six quantities are NaN wherever ``state`` is.  ``kin.eps_H``, ``kin.eta_par`` and ``abs(kin.omega)`` on the trajectories
+    are what ``GeneralisedAL.complete_analysis`` over the same grid predicts from the potential under the rapid-turn assumptions:
+    this is the map to lay beside it."""
+    state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
+    kin = kinematics(artifact, pars, state)
+    return (kin, state, n_end, status) if return_status else (kin, state, n_end)

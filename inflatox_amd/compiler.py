@@ -37,7 +37,7 @@ import numpy as np
 import sympy
 from sympy.printing.c import C99CodePrinter
 
-from .staging import HIPInflatoxPrinter, emit_eom_header, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
+from .staging import HIPInflatoxPrinter, emit_eom_header, emit_kinematics_header, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
 from .symbolic import InflationModel
 from .version import __abi_version__, __version__
 
@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._background_path = None
+        self._companion_paths = {}  # "background" / "kinematics" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -246,9 +246,7 @@ class CompilationArtifact:
             self._group_paths[group] = path
         return path
 
-    def eom_header_text(self) -> str:
-        """The generated header of the background equations of motion (``staging.emit_eom_header``), with this artefact's
-        parameter numbering and ``cse`` setting."""
+    def _trajectory_header_text(self, emitter) -> str:
         if self._eom_recipe is None:
             raise ValueError("this artefact does not know how it was compiled (not made by Compiler.compile)")
         model, params, use_cse, max_cses = self._eom_recipe
@@ -266,30 +264,58 @@ class CompilationArtifact:
             def cse_vector(vector):
                 return sympy.cse(list(vector), symbols=symbols(), list=True)
 
-        return emit_eom_header(model, params, cse=cse, cse_vector=cse_vector)
+        return emitter(model, params, cse=cse, cse_vector=cse_vector)
+
+    def eom_header_text(self) -> str:
+        """The generated header of the background equations of motion (``staging.emit_eom_header``), with this artefact's
+        parameter numbering and ``cse`` setting."""
+        return self._trajectory_header_text(emit_eom_header)
+
+    def kinematics_header_text(self) -> str:
+        """The generated header of the trajectory kinematics (``staging.emit_kinematics_header``), with this artefact's parameter
+        numbering and ``cse`` setting."""
+        return self._trajectory_header_text(emit_kinematics_header)
+
+    def _ensure_companion(self, what: str, sources: tuple, object_name: str, headers) -> str:
+        """``shared_object_path + "." + what``, where ``libinflx_hip.so`` looks for the companion object ``what``: built on first use by
+        one hipcc step from the core object's header and options plus the generated ``headers`` (``_build_companion_object``)."""
+        path = self._companion_paths.get(what)
+        if path is None or not os.path.exists(path):
+            if self._build is None or self._eom_recipe is None:
+                raise ValueError(f"this artefact does not know how it was compiled: its {what} object cannot be built (not made by Compiler.compile)")
+            header_text, options, tag = self._build
+            cached, log, code = _build_companion_object(header_text, options, tag, sources, object_name, headers())
+            if code != 0:
+                print(log.decode("utf-8", "replace"))
+                raise Exception(f"hipcc compiler error while building the {what} object (see previous output)")
+            path = self.shared_object_path + "." + what
+            tmp = path + f".{os.getpid()}.tmp"
+            shutil.copyfile(cached, tmp)
+            os.replace(tmp, path)
+            self._companion_paths[what] = path
+        return path
 
     def ensure_background(self) -> str:
         """Extension: build the background code object of this model -- the trajectory kernels of
         ``inflatox_amd.background`` (csrc/inflx_background_kernels.hip) -- and return its path, ``shared_object_path +
         ".background"``, where ``libinflx_hip.so`` looks for it.  One hipcc step on first use from the core object's header and
-        options plus a header of the equations of motion (``staging.emit_eom_header``), cached like everything else; the object
-        carries the core object's ``MODEL_TAG``.  It lies outside the kernel groups (``KERNEL_GROUPS``, ``inflx_groups``)."""
-        path = self._background_path
-        if path is None or not os.path.exists(path):
-            if self._build is None or self._eom_recipe is None:
-                raise ValueError("this artefact does not know how it was compiled: its background object cannot be built (not made by Compiler.compile)")
-            header_text, options, tag = self._build
-            eom_text = self.eom_header_text()
-            cached, log, code = _build_background_object(header_text, eom_text, options, tag)
-            if code != 0:
-                print(log.decode("utf-8", "replace"))
-                raise Exception("hipcc compiler error while building the background object (see previous output)")
-            path = self.shared_object_path + ".background"
-            tmp = path + f".{os.getpid()}.tmp"
-            shutil.copyfile(cached, tmp)
-            os.replace(tmp, path)
-            self._background_path = path
-        return path
+        options plus a header of the equations of motion (``staging.emit_eom_header``), cached like everything else as
+        ``<tag>.bg<hash>.hsaco`` (the hash covers the EoM header and the background sources, code only); the object carries the
+        core object's ``MODEL_TAG``.  It lies outside the kernel groups (``KERNEL_GROUPS``, ``inflx_groups``)."""
+        return self._ensure_companion("background", _BACKGROUND_SOURCES, "bg{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "eom{key}.h", self.eom_header_text())])
+
+    def ensure_kinematics(self) -> str:
+        """Extension: build the kinematics code object of this model -- the kernel of ``inflatox_amd.background.kinematics``
+        (csrc/inflx_kinematics_kernels.hip) -- and return its path, ``shared_object_path + ".kinematics"``, where
+        ``libinflx_hip.so`` looks for it.  One hipcc step on first use from the core object's header and options, the header of the
+        equations of motion and the kinematics header (``staging.emit_kinematics_header``), cached as ``<tag>.kin<hash>.hsaco``
+        (the hash covers the two generated headers and ``_KINEMATICS_SOURCES``, code only); the object carries the core object's
+        ``MODEL_TAG`` and a layout word of its own (``INFLX_KIN_ABI``).  Like the background object it lies outside the kernel
+        groups."""
+        return self._ensure_companion(
+            "kinematics", _KINEMATICS_SOURCES, "kin{key}.hsaco",
+            lambda: [("INFLX_EOM_HEADER", "kin{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "kin{key}.h", self.kinematics_header_text())],
+        )  # fmt: skip
 
     def ensure_all_groups(self) -> list[str]:
         """Extension: every group beside the core object (what a C client of ``libinflx_hip.so`` wants in place before it starts)."""
@@ -311,7 +337,7 @@ class CompilationArtifact:
 
     def __del__(self):
         if getattr(self, "auto_cleanup", False):
-            for path in [self.shared_object_path, *getattr(self, "_group_paths", {}).values(), getattr(self, "_background_path", None)]:
+            for path in [self.shared_object_path, *getattr(self, "_group_paths", {}).values(), *getattr(self, "_companion_paths", {}).values()]:
                 if path is None:
                     continue
                 try:
@@ -399,33 +425,37 @@ def _build_code_object(header_text: str, options: list[str], tag: str, groups: i
 
 
 _BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "inflx_background_abi.h", "inflx_background_rows.h")
+_KINEMATICS_SOURCES = ("inflx_kinematics_kernels.hip", "inflx_kinematics.h", "inflx_kinematics_abi.h")
 
 
-def _build_background_object(header_text: str, eom_text: str, options: list[str], tag: str):
-    """One hipcc step: the background kernels (csrc/inflx_background_kernels.hip) of the model whose core object has the content tag
-    ``tag`` (core header ``header_text``, hipcc ``options``) and whose equations of motion are ``eom_text``, into the content-addressed
-    cache as ``<tag>.bg<hash>.hsaco``; the hash covers the EoM header and the background sources (code only).  Returns (path, compiler
-    output, exit code)."""
+def _build_companion_object(header_text: str, options: list[str], tag: str, sources: tuple, object_name: str, headers: list):
+    """One hipcc step: a code object that goes with the core object of content tag ``tag`` (core header ``header_text``, hipcc
+    ``options``) -- the kernel file ``sources[0]`` with the generated ``headers``, a list of (macro that names the header, file name,
+    text) -- into the content-addressed cache.  ``object_name`` and the headers' file names are formats of ``key``, the hash over
+    the headers' texts and ``sources`` (code only); all of them get the prefix ``<tag>.``.  Returns (path, compiler output, exit
+    code)."""
     cache = _cache_dir()
-    h = hashlib.sha256(eom_text.encode())
-    for f in _BACKGROUND_SOURCES:
+    h = hashlib.sha256()
+    for _macro, _name, text in headers:
+        h.update(text.encode())
+    for f in sources:
         with open(os.path.join(_CSRC, f), "r", encoding="utf-8") as fh:
             h.update(_code_only(fh.read()).encode())
     key = h.hexdigest()[:12]
-    header_path = os.path.join(cache, f"{tag}.h")
-    eom_path = os.path.join(cache, f"{tag}.eom{key}.h")
-    cached = os.path.join(cache, f"{tag}.bg{key}.hsaco")
+    files = [("INFLX_MODEL_HEADER", os.path.join(cache, f"{tag}.h"), header_text)]
+    files += [(macro, os.path.join(cache, f"{tag}." + name.format(key=key)), text) for macro, name, text in headers]
+    cached = os.path.join(cache, f"{tag}." + object_name.format(key=key))
     log, code = b"", 0
     if not os.path.exists(cached):
-        for path, text in ((header_path, header_text), (eom_path, eom_text)):
+        for _macro, path, text in files:
             if not os.path.exists(path):
                 tmp = path + f".{os.getpid()}.tmp"
                 with open(tmp, "w") as fh:
                     fh.write(text)
                 os.replace(tmp, path)
         tmp_out = cached + f".{os.getpid()}.tmp"
-        cmd = [hipcc_path(), *options, f'-DINFLX_MODEL_TAG="{tag}"', f"-I{_CSRC}", f'-DINFLX_MODEL_HEADER="{header_path}"', f'-DINFLX_EOM_HEADER="{eom_path}"',
-               os.path.join(_CSRC, "inflx_background_kernels.hip"), "-o", tmp_out]  # fmt: skip
+        cmd = [hipcc_path(), *options, f'-DINFLX_MODEL_TAG="{tag}"', f"-I{_CSRC}", *[f'-D{macro}="{path}"' for macro, path, _text in files],
+               os.path.join(_CSRC, sources[0]), "-o", tmp_out]  # fmt: skip
         proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
         log, code = proc.stdout, proc.returncode
         if code == 0:

@@ -40,6 +40,7 @@
 #include "inflx_background_abi.h"
 #include "inflx_background_rows.h"
 #include "inflx_kernel_abi.h"
+#include "inflx_kinematics_abi.h"
 
 namespace {
 
@@ -422,6 +423,9 @@ struct inflx_model {
   hipFunction_t bg_target[2] = {};      // [method]: final-only with a target on N (inflx_solve_eom_to_efolds)
   hipFunction_t bg_sampled[2] = {};     // [method]: final-only with a list of samples (inflx_solve_eom_sampled)
   hipFunction_t bg_rows_transpose = nullptr;  // row planes -> (lanes, rows, 6) and (lanes, rows) (csrc/inflx_background_rows.h)
+  // trajectory kinematics (inflx_kinematics): the object `<artefact>.kinematics`, loaded on first use
+  hipModule_t kin_module = nullptr;
+  hipFunction_t kin_states = nullptr;
 };
 
 namespace {
@@ -1230,6 +1234,7 @@ void inflx_close(inflx_model* m) {
   if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
   for (hipModule_t extra : m->attached) (void)hipModuleUnload(extra);
   if (m->bg_module) (void)hipModuleUnload(m->bg_module);
+  if (m->kin_module) (void)hipModuleUnload(m->kin_module);
   if (m->module) (void)hipModuleUnload(m->module);
   delete m;
 }
@@ -3171,6 +3176,147 @@ int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_
       if (n_stored) n_stored[c0 + l] = (uint32_t)hc[INFLX_BG_CARRY_LAST_ROW * n + l];
     }
   }
+  return sf_verdict(m);
+}
+
+}  // extern "C"
+
+// ---- trajectory kinematics (inflx_kinematics) -------------------------------------------------------------------------------
+namespace {
+
+static_assert(kAbiMajor == INFLX_KIN_DEFAULT_ABI_MAJOR, "a kinematics object reports the core object's ABI major: change both together");
+
+// Load `<artefact>.kinematics` beside the core object: it must carry the core object's MODEL_TAG and this library's INFLX_KIN_ABI.
+int need_kinematics(inflx_model* m) {
+  if (m->kin_module) return INFLX_OK;
+  const std::string path = m->path + ".kinematics";
+  FILE* fh = fopen(path.c_str(), "rb");
+  if (!fh)
+    return fail(INFLX_ERR_SYMBOL, "the kinematics kernel of %s is not loaded and no %s exists: build it with CompilationArtifact.ensure_kinematics() "
+                "(inflatox_amd.background.kinematics does on first use)", m->path.c_str(), path.c_str());
+  fclose(fh);
+  HIP_TRY(hipSetDevice(m->device));
+  hipModule_t module = nullptr;
+  hipError_t e = hipModuleLoad(&module, path.c_str());
+  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
+  auto bail = [&](int code) {
+    const std::string first = g_last_error;
+    (void)hipModuleUnload(module);
+    g_last_error = first;
+    return code;
+  };
+  uint16_t version[3] = {};
+  uint32_t abi = 0;
+  char tag[128] = {0};
+  int rc;
+  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_KIN_ABI", &abi, sizeof abi, true)) ||
+      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
+    return bail(rc);
+  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_KIN_ABI_VERSION || m->tag != tag)
+    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
+                     "INFLX_KIN_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_KIN_ABI_VERSION));
+  hipFunction_t states = nullptr;
+  if (hipModuleGetFunction(&states, module, "inflx_kin_states") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_kin_states", path.c_str()));
+  m->kin_module = module;
+  m->kin_states = states;
+  note_sf_word(m, module);
+  return INFLX_OK;
+}
+
+// the argument checks inflx_kinematics and inflx_kinematics_device share; *span: the doubles of `states` the call reads
+int check_kinematics(inflx_model* m, const double* p, size_t P, size_t n_p, const void* states, size_t n, size_t ld, size_t traj_len, const void* out, size_t* span) {
+  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the kinematics require a 2-field model (model has %u fields)", m->dim);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
+  if (ld < 5) return fail(INFLX_ERR_SHAPE, "a state has five components: ld must be at least 5 (got %zu)", ld);
+  if (traj_len < 1) return fail(INFLX_ERR_ARG, "traj_len must be at least 1");
+  if (n % traj_len) return fail(INFLX_ERR_SHAPE, "%zu states are not a whole number of trajectories of %zu", n, traj_len);
+  if (P != 1 && P != n / traj_len) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, n / traj_len);
+  size_t doubles = 0;
+  if (n && (__builtin_mul_overflow(n - 1, ld, &doubles) || __builtin_add_overflow(doubles, (size_t)5, &doubles) || doubles > SIZE_MAX / sizeof(double) ||
+            n > SIZE_MAX / (INFLX_KIN_PLANES * sizeof(double))))
+    return fail(INFLX_ERR_SHAPE, "%zu states of stride %zu exceed the address space", n, ld);
+  if (n && !states) return fail(INFLX_ERR_ARG, "state array is NULL");
+  if (n && !out) return fail(INFLX_ERR_ARG, "output array is NULL");
+  *span = doubles;
+  return INFLX_OK;
+}
+
+struct KinBuffers {
+  double *p = nullptr, *y = nullptr, *out = nullptr;
+  ~KinBuffers() {
+    for (double* d : {p, y, out})
+      if (d) (void)hipFree(d);
+  }
+};
+
+// one launch: states [first, first + n) of the call, at d_y, into the planes d_out [6][n]
+int launch_kinematics(inflx_model* m, hipStream_t s, const double* d_y, const double* d_p, size_t p_stride, double* d_out, size_t n, size_t ld, size_t traj_len, size_t first) {
+  InflxKinArgs a;
+  memset(&a, 0, sizeof a);
+  a.y = d_y;
+  a.p = d_p;
+  a.out = d_out;
+  a.n = n;
+  a.ld = ld;
+  a.traj_len = traj_len;
+  a.p_stride = p_stride;
+  a.first = first;
+  void* params[] = {&a};
+  HIP_TRY(hipModuleLaunchKernel(m->kin_states, (unsigned)((n + INFLX_KIN_THREADS - 1) / INFLX_KIN_THREADS), 1, 1, INFLX_KIN_THREADS, 1, 1, 0, s, params, nullptr));
+  return INFLX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int inflx_kinematics(inflx_model* m, const double* p, size_t P, size_t n_p, const double* states, size_t n, size_t ld, size_t traj_len, double* out) {
+  INFLX_SERIALISE(m);
+  size_t span = 0;
+  int rc = check_kinematics(m, p, P, n_p, states, n, ld, traj_len, out, &span);
+  if (rc) return rc;
+  if (n == 0) return INFLX_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_kinematics(m))) return rc;
+  hipStream_t s = m->stream;
+  const size_t chunk = std::min(n, kBgMaxLanes);  // the lane bound of a pass of the solver
+  KinBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.y), ((chunk - 1) * ld + 5) * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), chunk * INFLX_KIN_PLANES * sizeof(double)));
+  for (size_t c0 = 0; c0 < n; c0 += chunk) {
+    const size_t nc = std::min(chunk, n - c0);
+    HIP_TRY(hipMemcpyAsync(buf.y, states + c0 * ld, ((nc - 1) * ld + 5) * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = launch_kinematics(m, s, buf.y, buf.p, P == 1 ? 0 : n_p, buf.out, nc, ld, traj_len, c0))) return rc;
+    // the six plane segments of this chunk: nc doubles each, n doubles apart in `out`
+    HIP_TRY(hipMemcpy2DAsync(out + c0, n * sizeof(double), buf.out, nc * sizeof(double), nc * sizeof(double), INFLX_KIN_PLANES, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return sf_verdict(m);
+}
+
+int inflx_kinematics_device(inflx_model* m, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n, size_t ld, size_t traj_len,
+                            void* d_out, size_t d_out_bytes, void* stream) {
+  INFLX_SERIALISE(m);
+  size_t span = 0;
+  int rc = check_kinematics(m, p, P, n_p, d_states, n, ld, traj_len, d_out, &span);
+  if (rc) return rc;
+  if (n && d_states_bytes < span * sizeof(double)) return fail(INFLX_ERR_SHAPE, "state buffer has %zu bytes, the call reads %zu", d_states_bytes, span * sizeof(double));
+  if (n && d_out_bytes < n * INFLX_KIN_PLANES * sizeof(double))
+    return fail(INFLX_ERR_SHAPE, "output buffer has %zu bytes, the call writes %zu", d_out_bytes, n * INFLX_KIN_PLANES * sizeof(double));
+  if ((n + INFLX_KIN_THREADS - 1) / INFLX_KIN_THREADS > 0x7fffffffu) return fail(INFLX_ERR_SHAPE, "%zu states exceed one launch (2^31 - 1 workgroups of %d)", n, INFLX_KIN_THREADS);
+  if (n == 0) return INFLX_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_kinematics(m))) return rc;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
+  KinBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  if ((rc = launch_kinematics(m, s, static_cast<const double*>(d_states), buf.p, P == 1 ? 0 : n_p, static_cast<double*>(d_out), n, ld, traj_len, 0))) return rc;
+  HIP_TRY(hipStreamSynchronize(s));  // (the parameter rows live until the kernel has read them)
   return sf_verdict(m);
 }
 

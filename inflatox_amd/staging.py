@@ -1087,3 +1087,58 @@ def emit_eom_header(model, param_slots: dict, cse=None, cse_vector=None) -> str:
         + "\n".join(lines)
         + "\n}\n"
     )
+
+
+def emit_kinematics_header(model, param_slots: dict, cse=None, cse_vector=None) -> str:
+    """The potential's slope along and across a velocity at one point, for the trajectory kinematics (csrc/inflx_kinematics.h):
+    ``inflx_kin_point(x0, x1, xd0, xd1, args, o)`` writes ``o[0]`` = d_a V xd^a, dV/dt along the trajectory, and ``o[1]`` =
+    (d_0 V xd_1 - d_1 V xd_0) / sqrt(det G) with xd_a = G_ab xd^b: the component of the gradient normal to the velocity times
+    |xd|_G, signed.  The cross form has no cancellation beyond what the data has (|dV|^2 - V_sigma^2 would).
+
+    A header of its own, read only by the kinematics code object (``CompilationArtifact.ensure_kinematics``).  Written like
+    ``emit_eom_header``: staged with every stage inline in one function, the model's ``cse`` setting (the gradient and the metric
+    each through ``cse_vector``), the velocities printed as ``xd0`` / ``xd1``; metric components that print as zero are skipped
+    and the rest added left to right."""
+    if model.dim != 2:
+        raise ValueError("the kinematics need a two-field model")
+    x0, x1 = model.coordinates
+    potential = sympy.sympify(model.potential)
+    gradient = [sympy.diff(potential, x0), sympy.diff(potential, x1)]
+    metric = [sympy.sympify(model.metric[i][j]) for i in range(2) for j in range(2)]
+    plain = C99CodePrinter()._print_Symbol
+    names = {x0: "x0", x1: "x1"}
+    for sym in set().union(*[e.free_symbols for e in gradient + metric]) - set(names):
+        names[sym] = param_slots[plain(sym)]
+    functions = [cse_vector(gradient) if cse_vector is not None else ([], gradient), cse_vector(metric) if cse_vector is not None else ([], metric)]
+    st = Stager(functions, x0, x1, names, staged=True)
+    lines = [ln for m in (U, R, C, P) for ln in st.lines[m]]
+    texts = list(st.outputs)
+    lines += [f"  const double dv0 = {texts[0]};", f"  const double dv1 = {texts[1]};"]
+    have = set()
+    for i in range(2):
+        for j in range(2):
+            t = texts[2 + 2 * i + j]
+            if t in ("0", "0.0"):
+                continue
+            have.add((i, j))
+            lines.append(f"  const double g{i}{j} = {t};")
+    for i in range(2):  # the lowered velocity xd_i = G_ij xd^j
+        lines.append(f"  const double xl{i} = 0.0" + "".join(f" + (g{i}{j} * xd{j})" for j in range(2) if (i, j) in have) + ";")
+    det = ["g00 * g11" if {(0, 0), (1, 1)} <= have else "0.0"]
+    if {(0, 1), (1, 0)} <= have:
+        det.append(" - g01 * g10")
+    lines += [
+        "  const double det = " + "".join(det) + ";",
+        "  o[0] = dv0 * xd0 + dv1 * xd1;",
+        "  o[1] = (dv0 * xl1 - dv1 * xl0) / sqrt(det);",
+    ]
+    return (
+        "// Generated by inflatox_amd.Compiler -- do not edit.\n"
+        f"// trajectory kinematics of model {model.model_name} (csrc/inflx_kinematics.h); needs the model's core header first\n"
+        "#pragma once\n"
+        "// o[0]: d_a V xd^a;  o[1]: (d_0 V xd_1 - d_1 V xd_0) / sqrt(det G), xd_a = G_ab xd^b\n"
+        "INFLX_FN void inflx_kin_point([[maybe_unused]] const double x0, [[maybe_unused]] const double x1, [[maybe_unused]] const double xd0, "
+        "[[maybe_unused]] const double xd1, [[maybe_unused]] const double* __restrict__ args, double* __restrict__ o) {\n"
+        + "\n".join(lines)
+        + "\n}\n"
+    )

@@ -16,7 +16,13 @@ substeps 4; best of three calls each, alternating, after a warm-up): ``solve_eom
 the calling thread: the path of every earlier version), the default ``solve_eom`` (transposed on the device, two contiguous
 copies) and ``solve_eom_batch_device`` followed by ``torch.cuda.synchronize()`` (nothing copied); a child process under ``rocprofv3
 --kernel-trace --stats`` makes one device-resident call, for the summed time of the ``inflx_bg_rows_transpose`` launches beside the
-``inflx_bg_advance_*`` launches.  Writes ``profiles/background_rows.json``.  Run from the repository root on the GPU box.
+``inflx_bg_advance_*`` launches.  Writes ``profiles/background_rows.json``.  ``--kinematics`` measures nothing but
+``background.kinematics``: its device path on 2^22 hyperbolic states read in place from (2^14, 256, 6) rows (ld = 6) -- the wall
+time of whole calls, each ending in a stream synchronise, and the ``inflx_kin_states`` kernel alone from a child process under
+``rocprofv3`` -- beside a device-to-device copy that moves as many bytes as the kernel reads plus writes, timed with device
+events in the same process; and the worst ratio of |result - 40-digit truth| to the allowance of tests/kinematics_reference.py
+over the zoo of tests/background_truth.py, for the host build and for the GPU.  Writes ``profiles/background_kinematics.json``.
+Run from the repository root on the GPU box.
 """
 
 import argparse
@@ -145,8 +151,10 @@ def rows_workload(log2_lanes=17, rows=256, substeps=4):
     print(json.dumps({"rows_workload_last_row_sum": int(np.minimum(sol.last_row, rows - 1).sum())}), flush=True)
 
 
-def _kernel_trace(log2_lanes):
-    """{kernel: [calls, total ns]} of the inflx_bg_* kernels of one device-resident call, from a child process under rocprofv3"""
+def _kernel_trace(log2_lanes, workload="--rows-workload", prefix="inflx_bg_", extra=(), each=()):
+    """{kernel: [calls, total ns]} of the kernels named ``prefix``* of the child process ``workload`` under rocprofv3 (by default
+    one device-resident call of the solver); ``extra``: further rocprofv3 options -- with ``--memory-copy-trace`` the memory copies
+    are listed the same way, by direction; ``each``: kernels whose single dispatches are listed too (``dispatch_ns``)"""
     import csv
     import glob
     import shutil
@@ -158,22 +166,38 @@ def _kernel_trace(log2_lanes):
         return {"error": "rocprofv3 not found"}
     out = tempfile.mkdtemp(prefix="background_rows_")
     try:
-        cmd = [prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__), "--rows-workload",
+        cmd = [prof, "--kernel-trace", *extra, "--stats", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__), workload,
                "--max-log2-lanes", str(log2_lanes)]  # fmt: skip
         proc = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
         if proc.returncode != 0:
             return {"error": f"rocprofv3 exit status {proc.returncode}", "stderr": proc.stderr[-1000:]}
         kernels = {}
-        for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
+        stats = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
+        if extra:
+            stats += glob.glob(os.path.join(out, "**", "*memory_copy_stats.csv"), recursive=True)
+        for path in stats:
             with open(path, newline="") as fh:
                 for row in csv.DictReader(fh):
-                    name = row["Name"].removesuffix(".kd")
-                    if name.startswith("inflx_bg_"):
+                    if not {"Name", "Calls", "TotalDurationNs"} <= set(row):
+                        continue
+                    name = row["Name"].removesuffix(".kd")[:120]
+                    if name.startswith(prefix):
                         calls, total = kernels.get(name, (0, 0))
                         kernels[name] = (calls + int(row["Calls"]), total + int(row["TotalDurationNs"]))
         if not kernels:
-            return {"error": "no inflx_bg_* kernel in the trace", "stdout": proc.stdout[-1000:]}
-        return {k: list(v) for k, v in sorted(kernels.items())}
+            return {"error": f"no {prefix}* kernel in the trace", "stdout": proc.stdout[-1000:]}
+        found = {k: list(v) for k, v in sorted(kernels.items())}
+        if each:
+            # the single dispatches of the kernels named in `each`: {name: durations in ns, longest first}
+            found["dispatch_ns"] = {}
+            for path in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True):
+                with open(path, newline="") as fh:
+                    for row in csv.DictReader(fh):
+                        if {"Kernel_Name", "Start_Timestamp", "End_Timestamp"} <= set(row) and row["Kernel_Name"].removesuffix(".kd") in each:
+                            found["dispatch_ns"].setdefault(row["Kernel_Name"].removesuffix(".kd"), []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+            for durations in found["dispatch_ns"].values():
+                durations.sort(reverse=True)
+        return found
     finally:
         shutil.rmtree(out, ignore_errors=True)
 
@@ -221,6 +245,133 @@ def rows_mode(log2_lanes=17, rows=256, substeps=4, repeats=3):
         json.dump(rec, fh, indent=1)
 
 
+KIN_LOG2_TRAJ, KIN_ROWS = 14, 256  # 2^14 trajectories x 256 rows = 2^22 states
+COPY_KERNEL = "__amd_rocclr_copyBuffer"  # what the HIP runtime carries a device-to-device copy out with
+KIN_SETS = 3  # input sets used in turn: 3 x 201 MB read and 201 MB written per call -- a line is long out of the 256 MiB Infinity Cache when its set comes round again
+
+
+def _kinematics_rows():
+    """(artefact, parameter row, KIN_SETS views (2^14, 256, 5) of (2^14, 256, 6) device rows): the first rows of 2^14 hyperbolic
+    trajectories, repeated along the row axis with a small shift per row and per set so that no two states are the same"""
+    import torch
+
+    spec, art, x, v = _rows_batch(KIN_LOG2_TRAJ)
+    sol = background.solve_eom_batch_device(art, spec.args, 2, x, v)
+    first = torch.cat([sol.states[:, :1], sol.N[:, :1, None]], dim=2)  # (B, 1, 6)
+    sets = []
+    for k in range(KIN_SETS):
+        shift = 1.0 + 1e-3 * (k / KIN_SETS + torch.arange(KIN_ROWS, dtype=torch.float64, device=first.device))[None, :, None]
+        sets.append((first * shift).contiguous()[:, :, :5])
+    return spec, art, sets
+
+
+def _copy_buffers(sets):
+    """(KIN_SETS sources, one destination) for the device-to-device copy that moves what one kinematics call moves: the call reads
+    the lines of (n, 6) rows and writes six planes, 96 bytes per state; a copy of 48 bytes per state reads and writes as much"""
+    import torch
+
+    n = sets[0].shape[0] * sets[0].shape[1]
+    srcs = [torch.empty(n * 6, dtype=torch.float64, device=sets[0].device).normal_() for _ in range(KIN_SETS)]
+    return srcs, torch.empty_like(srcs[0])
+
+
+def kinematics_workload(rounds=4):
+    """what the --kinematics mode runs under the profiler: a warm-up of both, then ``rounds`` x KIN_SETS device-resident calls and as
+    many device-to-device copies of the same bytes, each over input sets used in turn"""
+    import torch
+
+    spec, art, sets = _kinematics_rows()
+    srcs, dst = _copy_buffers(sets)
+    for r in range(rounds + 1):
+        for k in range(KIN_SETS):
+            kin = background.kinematics(art, spec.args, sets[k])
+        for k in range(KIN_SETS):
+            dst.copy_(srcs[k])
+        torch.cuda.synchronize()
+    print(json.dumps({"kinematics_workload_omega_nansum": float(torch.nansum(kin.omega))}), flush=True)
+
+
+def kinematics_accuracy():
+    """worst |result - truth| / allowance per model and quantity, host build and GPU (tests/kinematics_reference.py)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import background_truth as bt
+    import kinematics_reference as kr
+
+    rec = {}
+    for name in bt.GPU_MODELS:
+        states, pars = kr.zoo_states(name)
+        truth = kr.zoo_truth(name, 257)
+        host = kr.KinematicsTwin(bt.host_artifact(name)).kinematics(pars, states)
+        gpu = np.stack(background.kinematics(bt.device_artifact(name), pars, states))
+        allow = kr.allowance(truth, states[:, 4])
+        rec[name] = dict(host=kr.worst_ratios(host, truth, states[:, 4]), gpu=kr.worst_ratios(gpu, truth, states[:, 4]),
+                         gpu_to_host=dict(zip(kr.NAMES, (float(r) for r in (np.abs(gpu - host) / allow).max(axis=1)))))  # fmt: skip
+        print(json.dumps({name: rec[name]}), flush=True)
+    worst = {side: max(max(rec[m][side].values()) for m in rec) for side in ("host", "gpu", "gpu_to_host")}
+    return dict(states_per_model=257, allowance="tests/kinematics_reference.py allowance(): 1e-10 of the size of the terms a quantity is built from", worst=worst, models=rec)
+
+
+def kinematics_mode(repeats=8):
+    # first: this process has not opened the GPU yet.  Every kernel and every memory copy of the child, so that the copy is found
+    # whether the runtime makes it a kernel of its own or a copy-engine transfer
+    trace = _kernel_trace(KIN_LOG2_TRAJ, "--kinematics-workload", "", extra=("--memory-copy-trace",), each=("inflx_kin_states", COPY_KERNEL))
+    import torch
+
+    spec, art, sets = _kinematics_rows()
+    n = sets[0].shape[0] * sets[0].shape[1]
+    assert all(background._state_stride(tuple(y.shape), tuple(y.stride())) == 6 for y in sets)
+    srcs, dst = _copy_buffers(sets)
+    for k in range(KIN_SETS):
+        kin = background.kinematics(art, spec.args, sets[k])  # build / load / warm up
+        dst.copy_(srcs[k])
+    torch.cuda.synchronize()
+    moved = n * 6 * 8 + n * 6 * 8  # the lines of the (n, 6) rows read, the six planes written
+    t_call, t_copy = [], []
+    for _ in range(repeats):  # alternating, the input sets in turn
+        for k in range(KIN_SETS):
+            t0 = time.perf_counter()
+            kin = background.kinematics(art, spec.args, sets[k])  # (returns after its stream has been synchronised)
+            torch.cuda.synchronize()
+            t_call.append(time.perf_counter() - t0)
+        for k in range(KIN_SETS):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dst.copy_(srcs[k])
+            e1.record()
+            e1.synchronize()
+            t_copy.append(e0.elapsed_time(e1) * 1e-3)
+    # From the child's one trace: the kernel, and the copy as the runtime carries it out -- its copy kernel, which also serves the
+    # small uploads of the parameter row; the 15 large copies are its 15 longest dispatches.  Medians of the 15 of each.
+    want = KIN_SETS * 5
+    each = trace.get("dispatch_ns", {}) if isinstance(trace, dict) else {}
+    kernel_s = copy_trace_s = None
+    if len(each.get("inflx_kin_states", [])) == want:
+        kernel_s = float(np.median(each["inflx_kin_states"])) * 1e-9
+    if len(each.get(COPY_KERNEL, [])) >= want:
+        copy_trace_s = float(np.median(each[COPY_KERNEL][:want])) * 1e-9
+        each[COPY_KERNEL] = each[COPY_KERNEL][: want + 3]  # (the record keeps the large ones and the next three)
+    copy_s = float(np.median(t_copy))
+    rec = dict(model="hyperbolic", code_object=art._build[2], states=n, ld=6, traj_len=KIN_ROWS, read="plain per-lane loads (the one variant built)",
+               input_sets=KIN_SETS, bytes_moved=moved, repeats=repeats * KIN_SETS, call_s=dict(best=min(t_call), median=float(np.median(t_call))),
+               trace_ns=trace, kernel_s=kernel_s, copy_in_trace=COPY_KERNEL, copy_in_trace_s=copy_trace_s,
+               kernel_over_copy_in_trace=None if kernel_s is None or copy_trace_s is None else kernel_s / copy_trace_s,
+               d2d_copy_bytes=moved // 2, d2d_copy_events_s=dict(best=min(t_copy), median=copy_s), call_over_copy_events=float(np.median(t_call)) / copy_s,
+               finite=bool(torch.isfinite(kin.omega).all()),
+               note="call_s: wall time of background.kinematics on device rows (allocation and upload of the parameter row, one launch, a stream "
+                    "synchronise); trace_ns: [launches or transfers, summed ns] of every kernel and memory copy of a child process under rocprofv3 that "
+                    "makes 15 calls and 15 device-to-device copies of bytes_moved / 2 bytes (a copy reads and writes each), five rounds over three input "
+                    "sets used in turn, so that what a call or a copy reads was last touched 1.4 GB of traffic earlier; trace_ns.dispatch_ns: the single "
+                    "dispatches, longest first; kernel_s and copy_in_trace_s are the medians of the 15 kernel dispatches and of the 15 longest dispatches "
+                    "of the runtime's copy kernel (its others are small uploads), from the one trace; d2d_copy_events_s: the same copies between device events in this process (launch overhead "
+                    "included), alternating with the calls",
+               command="python scripts/background_probe.py --kinematics")  # fmt: skip
+    print(json.dumps(rec), flush=True)
+    rec["accuracy"] = kinematics_accuracy()
+    with open(os.path.join(ROOT, "profiles", "background_kinematics.json"), "w") as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", action="store_true", help="time the forced host scatter, the default host call and solve_eom_batch_device (B = 2^17, 256 rows), nothing else")
@@ -229,7 +380,15 @@ def main():
     ap.add_argument("--horizon-exit", action="store_true", help="time horizon_exit_map beside efolds_map at 1024^2 on hyperbolic, nothing else")
     ap.add_argument("--quick", action="store_true", help="B = 2^14 only (for a profiler run)")
     ap.add_argument("--max-log2-lanes", type=int, default=20)
+    ap.add_argument("--kinematics", action="store_true", help="time background.kinematics on 2^22 device-resident states beside a device-to-device copy, and record its accuracy; nothing else")
+    ap.add_argument("--kinematics-workload", action="store_true", help="a few device-resident kinematics calls (what --kinematics runs under rocprofv3)")
     args = ap.parse_args()
+    if args.kinematics_workload:
+        kinematics_workload()
+        return
+    if args.kinematics:
+        kinematics_mode()
+        return
     if args.rows_workload:
         rows_workload(min(args.max_log2_lanes, 17))
         return
