@@ -546,6 +546,40 @@ int inflx_kinematics(inflx_model* model, const double* p, size_t P, size_t n_p, 
 int inflx_kinematics_device(inflx_model* model, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n,
                             size_t ld, size_t traj_len, void* d_out, size_t d_out_bytes, void* stream);
 
+/*
+ * Entropic masses at n states (csrc/inflx_masses.h): like inflx_kinematics a post-pass over states, with the same arguments and the
+ * same T, N and sign of omega.  With V_;ab = d_a d_b V - Gamma^c_ab d_c V, kin = G_ab chi^a chi^b and n^b = eps^be chi_e /
+ * sqrt(det G), chi_e = G_ed chi^d (the unit normal times sigma_dot):
+ *   plane 0  V_TT   = V_;ab chi^a chi^b / kin, the covariant Hesse matrix along the velocity
+ *   plane 1  V_TN   = V_;ab chi^a n^b / kin
+ *   plane 2  V_NN   = V_;ab n^a n^b / kin, ... and across it
+ *   plane 3  ricci  = the Ricci scalar R = 2 K of the field-space metric: 2 / r^2 on a sphere, -2 / L^2 on diag(1, L^2 sinh^2(phi / L))
+ *   plane 4  eps_H  = kin / 2 / H^2, bit for bit inflx_kinematics' plane 0
+ *   plane 5  omega  = the signed turn rate per e-fold, bit for bit inflx_kinematics' plane 2
+ *   plane 6  M_eff2 = V_NN / H^2 + eps_H R - omega^2, the entropic mass of the sub-horizon Q_s equation in units of H^2
+ *   plane 7  mu_s2  = V_NN / H^2 + eps_H R + 3 omega^2, the super-horizon effective entropic mass in units of H^2
+ * IEEE arithmetic throughout.  A component of a state that is not finite (NaN, +-inf) gives eight NaNs there, whether or not the
+ * model depends on that component; a state at rest (kin = 0) gives eps_H = 0, a finite ricci and NaN in the other six.
+ *   p, states, traj_len   as for inflx_kinematics
+ *   out                   (8, n): the planes above
+ * The object `<artefact>.masses` (CompilationArtifact.ensure_masses()) is loaded on first use and must carry the artefact's MODEL_TAG
+ * and this library's layout word INFLX_MASS_ABI; INFLX_ERR_SYMBOL when it does not exist, INFLX_ERR_VERSION when it belongs to
+ * another model or layout.  It is independent of `<artefact>.background` and `<artefact>.kinematics`.  Arguments are checked before
+ * anything touches the device; n = 0 succeeds and launches nothing.  Runs on the handle's stream in chunks of at most 2^20 states --
+ * each copied in, evaluated and its eight plane segments copied out with one strided copy -- and returns when `out` is complete.  A
+ * USE_GSL artefact follows the error policy of inflx_solve_eom (inflx_sf_policy).
+ */
+int inflx_masses(inflx_model* model, const double* p, size_t P, size_t n_p, const double* states, size_t n, size_t ld, size_t traj_len, double* out);
+
+/*
+ * inflx_masses on device arrays: `d_states` (d_states_bytes >= ((n - 1) * ld + 5) * 8) and `d_out` (d_out_bytes >= 8 * n * 8) are
+ * device pointers, INFLX_ERR_SHAPE when a buffer is too small; `p` is a host array.  One launch on `stream` (a hipStream_t; NULL: the
+ * handle's stream); like inflx_kinematics_device the call returns after it has synchronised that stream.  No state and no result
+ * crosses to the host.
+ */
+int inflx_masses_device(inflx_model* model, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n, size_t ld,
+                        size_t traj_len, void* d_out, size_t d_out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,8 @@ SIGNATURES = {
     ),
     "inflx_kinematics": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, _DP]),
     "inflx_kinematics_device": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, C.c_void_p, _SIZE, _SIZE, _SIZE, _SIZE, C.c_void_p, _SIZE, C.c_void_p]),
+    "inflx_masses": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, _DP]),
+    "inflx_masses_device": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, C.c_void_p, _SIZE, _SIZE, _SIZE, _SIZE, C.c_void_p, _SIZE, C.c_void_p]),
 }
 
 
@@ -134,7 +136,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -555,6 +557,30 @@ class InflatoxDevLib:
         p = p.reshape(-1)
         _check(
             self._lib.inflx_kinematics_device(
+                self._h, _ptr(p), P, self.n_parameters, C.c_void_p(d_states_ptr), int(d_states_bytes), int(n), int(ld), int(traj_len), C.c_void_p(d_out_ptr),
+                int(d_out_bytes), C.c_void_p(stream),
+            )
+        )  # fmt: skip
+
+    # ---- entropic masses (include/inflx_hip.h: inflx_masses) -------------------------------------
+    def masses(self, p, states: np.ndarray, n: int, ld: int, traj_len: int = 1) -> np.ndarray:
+        """``kinematics``' arguments; returns (8, n): V_TT, V_TN, V_NN, ricci, eps_H, omega, M_eff2, mu_s2.  The masses object must be
+        in place (``CompilationArtifact.ensure_masses``)."""
+        p = _f64(p, "p")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((8, n))
+        _check(self._lib.inflx_masses(self._h, _ptr(p), P, self.n_parameters, _ptr(states), int(n), int(ld), int(traj_len), _ptr(out)))
+        return out
+
+    def masses_device(self, p, d_states_ptr: int, d_states_bytes: int, n: int, ld: int, traj_len: int, d_out_ptr: int, d_out_bytes: int, stream: int = 0) -> None:
+        """``masses`` on device arrays (include/inflx_hip.h: inflx_masses_device), with ``kinematics_device``'s arguments: the planes
+        (8, n) to ``d_out_ptr``."""
+        p = _f64(p, "p")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        _check(
+            self._lib.inflx_masses_device(
                 self._h, _ptr(p), P, self.n_parameters, C.c_void_p(d_states_ptr), int(d_states_bytes), int(n), int(ld), int(traj_len), C.c_void_p(d_out_ptr),
                 int(d_out_bytes), C.c_void_p(stream),
             )

@@ -11,7 +11,9 @@ of inflation from every grid point: the (phi, chi, H) at which ``complete_analys
 ``kinematics`` evaluates epsilon_H, eta_parallel, the turn rate per e-fold and the gradient along and across the velocity at any of
 these states -- host arrays, or the device-resident rows of ``solve_eom_batch_device`` without a byte crossing PCIe -- and
 ``turn_rate_map`` is ``horizon_exit_map`` followed by ``kinematics``: the measured counterpart, over the same grid, of what
-``GeneralisedAL.complete_analysis`` predicts from the potential alone.
+``GeneralisedAL.complete_analysis`` predicts from the potential alone.  ``masses`` evaluates the second-order counterpart at the same
+states -- the covariant Hesse matrix on the trajectory's own tangent and normal, the Ricci scalar of field space and the two entropic
+masses built from them -- and ``mass_map`` is ``horizon_exit_map`` followed by it.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -36,7 +38,7 @@ from ._native import InflatoxShapeError
 from .compiler import CompilationArtifact
 
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
-           "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics"]  # fmt: skip
+           "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -438,8 +440,15 @@ def kinematics(artifact: CompilationArtifact, pars, states) -> Kinematics:
     ``solve_eom_batch_device`` orders its result.  A tensor whose last stride is 1 and whose row stride is uniform --
     ``solve_eom_batch_device(...).states``, a view of the (B, steps, 6) rows -- is read in place, any other is made contiguous
     first.  Bad arguments raise ``InflatoxShapeError`` / ``ValueError`` before the device is touched."""
+    return _state_pass("kinematics", Kinematics, artifact, pars, states)
+
+
+def _state_pass(what: str, result, artifact: CompilationArtifact, pars, states):
+    """``kinematics`` and ``masses``: the pointwise pass ``what`` over ``states``, whose ``len(result._fields)`` planes come back as
+    the NamedTuple ``result``.  The object ``<artefact>.<what>`` is built on first use (``CompilationArtifact.ensure_<what>``)."""
+    planes = len(result._fields)
     if getattr(artifact, "n_fields", None) != 2:
-        raise InflatoxShapeError(f"the kinematics require a 2-field model (model has {getattr(artifact, 'n_fields', None)} fields)")
+        raise InflatoxShapeError(f"the {what} require a 2-field model (model has {getattr(artifact, 'n_fields', None)} fields)")
     on_device = type(states).__module__.split(".")[0] == "torch" and bool(getattr(states, "is_cuda", False))
     if on_device:
         import torch
@@ -462,33 +471,33 @@ def kinematics(artifact: CompilationArtifact, pars, states) -> Kinematics:
     traj_len = shape[1] if len(shape) == 3 else 1
     p = _pars(artifact, pars, lead[0] if lead else 1)
     if on_device:
-        out = torch.empty((6, n), dtype=torch.float64, device=y.device)
+        out = torch.empty((planes, n), dtype=torch.float64, device=y.device)
         if n:
             ld = _state_stride(shape, tuple(y.stride()))
             if ld is None:
                 y, ld = y.contiguous(), 5
             lib = _dylib(artifact, background=False)
-            artifact.ensure_kinematics()
+            getattr(artifact, "ensure_" + what)()
             if getattr(artifact, "_background_torch_stream", None) is None:
                 artifact._background_torch_stream = torch.cuda.Stream(device=y.device)
             side = artifact._background_torch_stream
             consumer = torch.cuda.current_stream(y.device)
             side.wait_stream(consumer)  # the states were written, and `out` allocated, on the consumer's stream
             held = y.untyped_storage().nbytes() - y.storage_offset() * 8  # what the tensor's storage holds from its first element on
-            lib.kinematics_device(p, y.data_ptr(), held, n, ld, traj_len, out.data_ptr(), out.numel() * 8, stream=side.cuda_stream)
+            getattr(lib, what + "_device")(p, y.data_ptr(), held, n, ld, traj_len, out.data_ptr(), out.numel() * 8, stream=side.cuda_stream)
             consumer.wait_stream(side)
             y.record_stream(side)
             out.record_stream(side)
-        return Kinematics(*out.reshape((6, *lead)))
+        return result(*out.reshape((planes, *lead)))
     if n == 0:
-        return Kinematics(*np.empty((6, *lead)))
+        return result(*np.empty((planes, *lead)))
     ld = _state_stride(shape, tuple(st // 8 if st % 8 == 0 else 0 for st in y.strides))
     if ld is None or ld > _HOST_MAX_LD:
         y, ld = np.ascontiguousarray(y), 5
     lib = _dylib(artifact, background=False)
-    artifact.ensure_kinematics()
-    out = lib.kinematics(p, y, n, ld, traj_len)
-    return Kinematics(*out.reshape((6, *lead)))
+    getattr(artifact, "ensure_" + what)()
+    out = getattr(lib, what)(p, y, n, ld, traj_len)
+    return result(*out.reshape((planes, *lead)))
 
 
 def turn_rate_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, derivatives_init=(0.0, 0.0),
@@ -502,3 +511,45 @@ def turn_rate_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: 
     state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
     kin = kinematics(artifact, pars, state)
     return (kin, state, n_end, status) if return_status else (kin, state, n_end)
+
+
+class Masses(NamedTuple):
+    """What :func:`masses` returns, each member of the shape of the states' leading axes and all eight views of one (8, ...) array.
+    T = chi / sigma_dot and N are the trajectory's own tangent and normal, in :class:`Kinematics`' orientation.  ``V_TT``, ``V_TN``,
+    ``V_NN``: the covariant Hesse matrix V_;ab = d_a d_b V - Gamma^c_ab d_c V on (T, T), (T, N) and (N, N); ``ricci``: the Ricci scalar
+    R of the field-space metric (2 / r^2 on a sphere, -2 / L^2 on the hyperbolic metric diag(1, L^2 sinh^2(phi / L))); ``eps_H`` and
+    ``omega``: :class:`Kinematics`' values, bit for bit; ``M_eff2`` = V_NN / H^2 + eps_H R - omega^2, the entropic mass in the
+    sub-horizon equation of Q_s, and ``mu_s2`` = V_NN / H^2 + eps_H R + 3 omega^2, the super-horizon effective entropic mass, both in
+    units of H^2."""
+
+    V_TT: np.ndarray
+    V_TN: np.ndarray
+    V_NN: np.ndarray
+    ricci: np.ndarray
+    eps_H: np.ndarray
+    omega: np.ndarray
+    M_eff2: np.ndarray
+    mu_s2: np.ndarray
+
+
+def masses(artifact: CompilationArtifact, pars, states) -> Masses:
+    """The covariant Hesse matrix along and across the velocity, the curvature of field space and the entropic masses at ``states``:
+    :func:`kinematics`' arguments, shapes ((5,), (n, 5), (B, S, 5)), parameter-row rules and argument checks, and its two paths -- a
+    numpy array is evaluated in chunks of at most 2^20 states and returns numpy arrays, a ``torch.float64`` GPU tensor such as
+    ``solve_eom_batch_device(...).states`` is read in place and returns tensors.  A pointwise pass of one GPU lane per state
+    (csrc/inflx_masses.h); the kernel is built into ``<artefact>.masses`` on first use (``CompilationArtifact.ensure_masses``), and
+    neither the integrator nor the kinematics object is involved.  A component that is not finite (NaN, +-inf) gives eight NaNs,
+    whether or not the model depends on that component; a state at rest (sigma_dot = 0) has eps_H = 0, a finite ``ricci`` and NaN
+    elsewhere."""
+    return _state_pass("masses", Masses, artifact, pars, states)
+
+
+def mass_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, derivatives_init=(0.0, 0.0),
+             max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """``horizon_exit_map`` (same arguments) followed by ``masses`` at the exit states: ``(masses, state, N_end)`` with ``masses`` the
+    :class:`Masses` of (N0, N1) arrays at the state ``N_star`` e-folds before the end of inflation from every grid point, and
+    ``state`` (N0, N1, 5) and ``N_end`` (N0, N1) exactly ``horizon_exit_map``'s; ``return_status=True`` adds its (N0, N1) status map.
+    All eight quantities are NaN wherever ``state`` is."""
+    state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
+    mass = masses(artifact, pars, state)
+    return (mass, state, n_end, status) if return_status else (mass, state, n_end)

@@ -37,7 +37,7 @@ import numpy as np
 import sympy
 from sympy.printing.c import C99CodePrinter
 
-from .staging import HIPInflatoxPrinter, emit_eom_header, emit_kinematics_header, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
+from .staging import HIPInflatoxPrinter, emit_eom_header, emit_kinematics_header, emit_masses_header, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
 from .symbolic import InflationModel
 from .version import __abi_version__, __version__
 
@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -276,6 +276,11 @@ class CompilationArtifact:
         numbering and ``cse`` setting."""
         return self._trajectory_header_text(emit_kinematics_header)
 
+    def masses_header_text(self) -> str:
+        """The generated header of the covariant Hesse matrix along a trajectory and the Ricci scalar
+        (``staging.emit_masses_header``), with this artefact's parameter numbering and ``cse`` setting."""
+        return self._trajectory_header_text(emit_masses_header)
+
     def _ensure_companion(self, what: str, sources: tuple, object_name: str, headers) -> str:
         """``shared_object_path + "." + what``, where ``libinflx_hip.so`` looks for the companion object ``what``: built on first use by
         one hipcc step from the core object's header and options plus the generated ``headers`` (``_build_companion_object``)."""
@@ -315,6 +320,20 @@ class CompilationArtifact:
         return self._ensure_companion(
             "kinematics", _KINEMATICS_SOURCES, "kin{key}.hsaco",
             lambda: [("INFLX_EOM_HEADER", "kin{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "kin{key}.h", self.kinematics_header_text())],
+        )  # fmt: skip
+
+    def ensure_masses(self) -> str:
+        """Extension: build the masses code object of this model -- the kernel of ``inflatox_amd.background.masses``
+        (csrc/inflx_masses_kernels.hip) -- and return its path, ``shared_object_path + ".masses"``, where ``libinflx_hip.so`` looks
+        for it.  One hipcc step on first use from the core object's header and options, the header of the equations of motion, the
+        kinematics header and the masses header (``staging.emit_masses_header``), cached as ``<tag>.mass<hash>.hsaco`` (the hash
+        covers the three generated headers and ``_MASSES_SOURCES``, code only); the object carries the core object's ``MODEL_TAG``
+        and a layout word of its own (``INFLX_MASS_ABI``).  Like the background and kinematics objects it lies outside the kernel
+        groups, and neither of them is involved."""
+        return self._ensure_companion(
+            "masses", _MASSES_SOURCES, "mass{key}.hsaco",
+            lambda: [("INFLX_EOM_HEADER", "mass{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "mass{key}.kin.h", self.kinematics_header_text()),
+                     ("INFLX_MASS_HEADER", "mass{key}.h", self.masses_header_text())],
         )  # fmt: skip
 
     def ensure_all_groups(self) -> list[str]:
@@ -426,6 +445,7 @@ def _build_code_object(header_text: str, options: list[str], tag: str, groups: i
 
 _BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "inflx_background_abi.h", "inflx_background_rows.h")
 _KINEMATICS_SOURCES = ("inflx_kinematics_kernels.hip", "inflx_kinematics.h", "inflx_kinematics_abi.h")
+_MASSES_SOURCES = ("inflx_masses_kernels.hip", "inflx_masses.h", "inflx_masses_abi.h")
 
 
 def _build_companion_object(header_text: str, options: list[str], tag: str, sources: tuple, object_name: str, headers: list):

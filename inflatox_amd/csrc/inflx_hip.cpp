@@ -41,6 +41,7 @@
 #include "inflx_background_rows.h"
 #include "inflx_kernel_abi.h"
 #include "inflx_kinematics_abi.h"
+#include "inflx_masses_abi.h"
 
 namespace {
 
@@ -426,6 +427,9 @@ struct inflx_model {
   // trajectory kinematics (inflx_kinematics): the object `<artefact>.kinematics`, loaded on first use
   hipModule_t kin_module = nullptr;
   hipFunction_t kin_states = nullptr;
+  // entropic masses (inflx_masses): the object `<artefact>.masses`, loaded on first use
+  hipModule_t mass_module = nullptr;
+  hipFunction_t mass_states = nullptr;
 };
 
 namespace {
@@ -1235,6 +1239,7 @@ void inflx_close(inflx_model* m) {
   for (hipModule_t extra : m->attached) (void)hipModuleUnload(extra);
   if (m->bg_module) (void)hipModuleUnload(m->bg_module);
   if (m->kin_module) (void)hipModuleUnload(m->kin_module);
+  if (m->mass_module) (void)hipModuleUnload(m->mass_module);
   if (m->module) (void)hipModuleUnload(m->module);
   delete m;
 }
@@ -3181,19 +3186,36 @@ int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_
 
 }  // extern "C"
 
-// ---- trajectory kinematics (inflx_kinematics) -------------------------------------------------------------------------------
+// ---- pointwise passes over states: trajectory kinematics (inflx_kinematics) and entropic masses (inflx_masses) ----------------
 namespace {
 
 static_assert(kAbiMajor == INFLX_KIN_DEFAULT_ABI_MAJOR, "a kinematics object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_MASS_DEFAULT_ABI_MAJOR, "a masses object reports the core object's ABI major: change both together");
+static_assert(sizeof(InflxMassArgs) == sizeof(InflxKinArgs), "InflxMassArgs has the fields of InflxKinArgs");
 
-// Load `<artefact>.kinematics` beside the core object: it must carry the core object's MODEL_TAG and this library's INFLX_KIN_ABI.
-int need_kinematics(inflx_model* m) {
-  if (m->kin_module) return INFLX_OK;
-  const std::string path = m->path + ".kinematics";
+// One such pass: a kernel of one lane per state in a code object of its own, `<artefact>.<what>`, which
+// CompilationArtifact.ensure_<what>() builds and inflatox_amd.background.<what> calls.
+struct StatePass {
+  const char* what;
+  const char* abi_symbol;  // the object's layout word
+  uint32_t abi;            // ... and this library's value of it
+  const char* kernel;
+  unsigned threads;
+  size_t planes;  // quantities per state
+  hipModule_t inflx_model::*module;
+  hipFunction_t inflx_model::*states;
+};
+const StatePass kKinematics = {"kinematics", "INFLX_KIN_ABI", INFLX_KIN_ABI_VERSION, "inflx_kin_states", INFLX_KIN_THREADS, INFLX_KIN_PLANES, &inflx_model::kin_module, &inflx_model::kin_states};
+const StatePass kMasses = {"masses", "INFLX_MASS_ABI", INFLX_MASS_ABI_VERSION, "inflx_mass_states", INFLX_MASS_THREADS, INFLX_MASS_PLANES, &inflx_model::mass_module, &inflx_model::mass_states};
+
+// Load `<artefact>.<what>` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
+int need_state_pass(inflx_model* m, const StatePass& pass) {
+  if (m->*pass.module) return INFLX_OK;
+  const std::string path = m->path + "." + pass.what;
   FILE* fh = fopen(path.c_str(), "rb");
   if (!fh)
-    return fail(INFLX_ERR_SYMBOL, "the kinematics kernel of %s is not loaded and no %s exists: build it with CompilationArtifact.ensure_kinematics() "
-                "(inflatox_amd.background.kinematics does on first use)", m->path.c_str(), path.c_str());
+    return fail(INFLX_ERR_SYMBOL, "the %s kernel of %s is not loaded and no %s exists: build it with CompilationArtifact.ensure_%s() "
+                "(inflatox_amd.background.%s does on first use)", pass.what, m->path.c_str(), path.c_str(), pass.what, pass.what);
   fclose(fh);
   HIP_TRY(hipSetDevice(m->device));
   hipModule_t module = nullptr;
@@ -3209,24 +3231,25 @@ int need_kinematics(inflx_model* m) {
   uint32_t abi = 0;
   char tag[128] = {0};
   int rc;
-  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_KIN_ABI", &abi, sizeof abi, true)) ||
+  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), pass.abi_symbol, &abi, sizeof abi, true)) ||
       (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
     return bail(rc);
-  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_KIN_ABI_VERSION || m->tag != tag)
+  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != pass.abi || m->tag != tag)
     return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
-                     "INFLX_KIN_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_KIN_ABI_VERSION));
+                     "%s %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), pass.abi_symbol, abi, (unsigned)pass.abi));
   hipFunction_t states = nullptr;
-  if (hipModuleGetFunction(&states, module, "inflx_kin_states") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_kin_states", path.c_str()));
-  m->kin_module = module;
-  m->kin_states = states;
+  if (hipModuleGetFunction(&states, module, pass.kernel) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), pass.kernel));
+  m->*pass.module = module;
+  m->*pass.states = states;
   note_sf_word(m, module);
   return INFLX_OK;
 }
 
-// the argument checks inflx_kinematics and inflx_kinematics_device share; *span: the doubles of `states` the call reads
-int check_kinematics(inflx_model* m, const double* p, size_t P, size_t n_p, const void* states, size_t n, size_t ld, size_t traj_len, const void* out, size_t* span) {
+// the argument checks the host and the device form of a pass share; *span: the doubles of `states` the call reads
+int check_state_pass(inflx_model* m, const StatePass& pass, const double* p, size_t P, size_t n_p, const void* states, size_t n, size_t ld, size_t traj_len, const void* out,
+                     size_t* span) {
   if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the kinematics require a 2-field model (model has %u fields)", m->dim);
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the %s require a 2-field model (model has %u fields)", pass.what, m->dim);
   if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
   if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
   if (ld < 5) return fail(INFLX_ERR_SHAPE, "a state has five components: ld must be at least 5 (got %zu)", ld);
@@ -3235,7 +3258,7 @@ int check_kinematics(inflx_model* m, const double* p, size_t P, size_t n_p, cons
   if (P != 1 && P != n / traj_len) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, n / traj_len);
   size_t doubles = 0;
   if (n && (__builtin_mul_overflow(n - 1, ld, &doubles) || __builtin_add_overflow(doubles, (size_t)5, &doubles) || doubles > SIZE_MAX / sizeof(double) ||
-            n > SIZE_MAX / (INFLX_KIN_PLANES * sizeof(double))))
+            n > SIZE_MAX / (pass.planes * sizeof(double))))
     return fail(INFLX_ERR_SHAPE, "%zu states of stride %zu exceed the address space", n, ld);
   if (n && !states) return fail(INFLX_ERR_ARG, "state array is NULL");
   if (n && !out) return fail(INFLX_ERR_ARG, "output array is NULL");
@@ -3251,9 +3274,11 @@ struct KinBuffers {
   }
 };
 
-// one launch: states [first, first + n) of the call, at d_y, into the planes d_out [6][n]
-int launch_kinematics(inflx_model* m, hipStream_t s, const double* d_y, const double* d_p, size_t p_stride, double* d_out, size_t n, size_t ld, size_t traj_len, size_t first) {
-  InflxKinArgs a;
+// one launch: states [first, first + n) of the call, at d_y, into the planes d_out [pass.planes][n].  Args: InflxKinArgs or InflxMassArgs
+template <class Args>
+int launch_state_pass(inflx_model* m, const StatePass& pass, hipStream_t s, const double* d_y, const double* d_p, size_t p_stride, double* d_out, size_t n, size_t ld,
+                      size_t traj_len, size_t first) {
+  Args a;
   memset(&a, 0, sizeof a);
   a.y = d_y;
   a.p = d_p;
@@ -3264,8 +3289,58 @@ int launch_kinematics(inflx_model* m, hipStream_t s, const double* d_y, const do
   a.p_stride = p_stride;
   a.first = first;
   void* params[] = {&a};
-  HIP_TRY(hipModuleLaunchKernel(m->kin_states, (unsigned)((n + INFLX_KIN_THREADS - 1) / INFLX_KIN_THREADS), 1, 1, INFLX_KIN_THREADS, 1, 1, 0, s, params, nullptr));
+  HIP_TRY(hipModuleLaunchKernel(m->*pass.states, (unsigned)((n + pass.threads - 1) / pass.threads), 1, 1, pass.threads, 1, 1, 0, s, params, nullptr));
   return INFLX_OK;
+}
+
+// the host form: chunks of at most 2^20 states, each copied in, evaluated and its plane segments copied out
+template <class Args>
+int state_pass_host(inflx_model* m, const StatePass& pass, const double* p, size_t P, size_t n_p, const double* states, size_t n, size_t ld, size_t traj_len, double* out) {
+  size_t span = 0;
+  int rc = check_state_pass(m, pass, p, P, n_p, states, n, ld, traj_len, out, &span);
+  if (rc) return rc;
+  if (n == 0) return INFLX_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_state_pass(m, pass))) return rc;
+  hipStream_t s = m->stream;
+  const size_t chunk = std::min(n, kBgMaxLanes);  // the lane bound of a pass of the solver
+  KinBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.y), ((chunk - 1) * ld + 5) * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), chunk * pass.planes * sizeof(double)));
+  for (size_t c0 = 0; c0 < n; c0 += chunk) {
+    const size_t nc = std::min(chunk, n - c0);
+    HIP_TRY(hipMemcpyAsync(buf.y, states + c0 * ld, ((nc - 1) * ld + 5) * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = launch_state_pass<Args>(m, pass, s, buf.y, buf.p, P == 1 ? 0 : n_p, buf.out, nc, ld, traj_len, c0))) return rc;
+    // the plane segments of this chunk: nc doubles each, n doubles apart in `out`
+    HIP_TRY(hipMemcpy2DAsync(out + c0, n * sizeof(double), buf.out, nc * sizeof(double), nc * sizeof(double), pass.planes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return sf_verdict(m);
+}
+
+// the device form: one launch on the caller's stream, synchronised before it returns
+template <class Args>
+int state_pass_device(inflx_model* m, const StatePass& pass, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n, size_t ld,
+                      size_t traj_len, void* d_out, size_t d_out_bytes, void* stream) {
+  size_t span = 0;
+  int rc = check_state_pass(m, pass, p, P, n_p, d_states, n, ld, traj_len, d_out, &span);
+  if (rc) return rc;
+  if (n && d_states_bytes < span * sizeof(double)) return fail(INFLX_ERR_SHAPE, "state buffer has %zu bytes, the call reads %zu", d_states_bytes, span * sizeof(double));
+  if (n && d_out_bytes < n * pass.planes * sizeof(double))
+    return fail(INFLX_ERR_SHAPE, "output buffer has %zu bytes, the call writes %zu", d_out_bytes, n * pass.planes * sizeof(double));
+  if ((n + pass.threads - 1) / pass.threads > 0x7fffffffu) return fail(INFLX_ERR_SHAPE, "%zu states exceed one launch (2^31 - 1 workgroups of %u)", n, pass.threads);
+  if (n == 0) return INFLX_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_state_pass(m, pass))) return rc;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
+  KinBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  if ((rc = launch_state_pass<Args>(m, pass, s, static_cast<const double*>(d_states), buf.p, P == 1 ? 0 : n_p, static_cast<double*>(d_out), n, ld, traj_len, 0))) return rc;
+  HIP_TRY(hipStreamSynchronize(s));  // (the parameter rows live until the kernel has read them)
+  return sf_verdict(m);
 }
 
 }  // namespace
@@ -3274,50 +3349,24 @@ extern "C" {
 
 int inflx_kinematics(inflx_model* m, const double* p, size_t P, size_t n_p, const double* states, size_t n, size_t ld, size_t traj_len, double* out) {
   INFLX_SERIALISE(m);
-  size_t span = 0;
-  int rc = check_kinematics(m, p, P, n_p, states, n, ld, traj_len, out, &span);
-  if (rc) return rc;
-  if (n == 0) return INFLX_OK;
-  HIP_TRY(hipSetDevice(m->device));
-  if ((rc = need_kinematics(m))) return rc;
-  hipStream_t s = m->stream;
-  const size_t chunk = std::min(n, kBgMaxLanes);  // the lane bound of a pass of the solver
-  KinBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.y), ((chunk - 1) * ld + 5) * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), chunk * INFLX_KIN_PLANES * sizeof(double)));
-  for (size_t c0 = 0; c0 < n; c0 += chunk) {
-    const size_t nc = std::min(chunk, n - c0);
-    HIP_TRY(hipMemcpyAsync(buf.y, states + c0 * ld, ((nc - 1) * ld + 5) * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = launch_kinematics(m, s, buf.y, buf.p, P == 1 ? 0 : n_p, buf.out, nc, ld, traj_len, c0))) return rc;
-    // the six plane segments of this chunk: nc doubles each, n doubles apart in `out`
-    HIP_TRY(hipMemcpy2DAsync(out + c0, n * sizeof(double), buf.out, nc * sizeof(double), nc * sizeof(double), INFLX_KIN_PLANES, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  return sf_verdict(m);
+  return state_pass_host<InflxKinArgs>(m, kKinematics, p, P, n_p, states, n, ld, traj_len, out);
 }
 
 int inflx_kinematics_device(inflx_model* m, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n, size_t ld, size_t traj_len,
                             void* d_out, size_t d_out_bytes, void* stream) {
   INFLX_SERIALISE(m);
-  size_t span = 0;
-  int rc = check_kinematics(m, p, P, n_p, d_states, n, ld, traj_len, d_out, &span);
-  if (rc) return rc;
-  if (n && d_states_bytes < span * sizeof(double)) return fail(INFLX_ERR_SHAPE, "state buffer has %zu bytes, the call reads %zu", d_states_bytes, span * sizeof(double));
-  if (n && d_out_bytes < n * INFLX_KIN_PLANES * sizeof(double))
-    return fail(INFLX_ERR_SHAPE, "output buffer has %zu bytes, the call writes %zu", d_out_bytes, n * INFLX_KIN_PLANES * sizeof(double));
-  if ((n + INFLX_KIN_THREADS - 1) / INFLX_KIN_THREADS > 0x7fffffffu) return fail(INFLX_ERR_SHAPE, "%zu states exceed one launch (2^31 - 1 workgroups of %d)", n, INFLX_KIN_THREADS);
-  if (n == 0) return INFLX_OK;
-  HIP_TRY(hipSetDevice(m->device));
-  if ((rc = need_kinematics(m))) return rc;
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
-  KinBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  if ((rc = launch_kinematics(m, s, static_cast<const double*>(d_states), buf.p, P == 1 ? 0 : n_p, static_cast<double*>(d_out), n, ld, traj_len, 0))) return rc;
-  HIP_TRY(hipStreamSynchronize(s));  // (the parameter rows live until the kernel has read them)
-  return sf_verdict(m);
+  return state_pass_device<InflxKinArgs>(m, kKinematics, p, P, n_p, d_states, d_states_bytes, n, ld, traj_len, d_out, d_out_bytes, stream);
+}
+
+int inflx_masses(inflx_model* m, const double* p, size_t P, size_t n_p, const double* states, size_t n, size_t ld, size_t traj_len, double* out) {
+  INFLX_SERIALISE(m);
+  return state_pass_host<InflxMassArgs>(m, kMasses, p, P, n_p, states, n, ld, traj_len, out);
+}
+
+int inflx_masses_device(inflx_model* m, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n, size_t ld, size_t traj_len, void* d_out,
+                        size_t d_out_bytes, void* stream) {
+  INFLX_SERIALISE(m);
+  return state_pass_device<InflxMassArgs>(m, kMasses, p, P, n_p, d_states, d_states_bytes, n, ld, traj_len, d_out, d_out_bytes, stream);
 }
 
 }  // extern "C"

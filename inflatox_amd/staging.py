@@ -1089,6 +1089,25 @@ def emit_eom_header(model, param_slots: dict, cse=None, cse_vector=None) -> str:
     )
 
 
+def _lowered_velocity(metric_texts) -> tuple:
+    """(statements, det G as text) for the kinematics and masses headers, from the printed metric components g00, g01, g10, g11:
+    the components that do not print as zero as ``g<i><j>``, and the lowered velocity ``xl<i>`` = G_ij xd^j added left to right."""
+    lines, have = [], set()
+    for i in range(2):
+        for j in range(2):
+            t = metric_texts[2 * i + j]
+            if t in ("0", "0.0"):
+                continue
+            have.add((i, j))
+            lines.append(f"  const double g{i}{j} = {t};")
+    for i in range(2):
+        lines.append(f"  const double xl{i} = 0.0" + "".join(f" + (g{i}{j} * xd{j})" for j in range(2) if (i, j) in have) + ";")
+    det = "g00 * g11" if {(0, 0), (1, 1)} <= have else "0.0"
+    if {(0, 1), (1, 0)} <= have:
+        det += " - g01 * g10"
+    return lines, det
+
+
 def emit_kinematics_header(model, param_slots: dict, cse=None, cse_vector=None) -> str:
     """The potential's slope along and across a velocity at one point, for the trajectory kinematics (csrc/inflx_kinematics.h):
     ``inflx_kin_point(x0, x1, xd0, xd1, args, o)`` writes ``o[0]`` = d_a V xd^a, dV/dt along the trajectory, and ``o[1]`` =
@@ -1114,21 +1133,10 @@ def emit_kinematics_header(model, param_slots: dict, cse=None, cse_vector=None) 
     lines = [ln for m in (U, R, C, P) for ln in st.lines[m]]
     texts = list(st.outputs)
     lines += [f"  const double dv0 = {texts[0]};", f"  const double dv1 = {texts[1]};"]
-    have = set()
-    for i in range(2):
-        for j in range(2):
-            t = texts[2 + 2 * i + j]
-            if t in ("0", "0.0"):
-                continue
-            have.add((i, j))
-            lines.append(f"  const double g{i}{j} = {t};")
-    for i in range(2):  # the lowered velocity xd_i = G_ij xd^j
-        lines.append(f"  const double xl{i} = 0.0" + "".join(f" + (g{i}{j} * xd{j})" for j in range(2) if (i, j) in have) + ";")
-    det = ["g00 * g11" if {(0, 0), (1, 1)} <= have else "0.0"]
-    if {(0, 1), (1, 0)} <= have:
-        det.append(" - g01 * g10")
+    metric_lines, det = _lowered_velocity(texts[2:6])
+    lines += metric_lines
     lines += [
-        "  const double det = " + "".join(det) + ";",
+        "  const double det = " + det + ";",
         "  o[0] = dv0 * xd0 + dv1 * xd1;",
         "  o[1] = (dv0 * xl1 - dv1 * xl0) / sqrt(det);",
     ]
@@ -1138,6 +1146,75 @@ def emit_kinematics_header(model, param_slots: dict, cse=None, cse_vector=None) 
         "#pragma once\n"
         "// o[0]: d_a V xd^a;  o[1]: (d_0 V xd_1 - d_1 V xd_0) / sqrt(det G), xd_a = G_ab xd^b\n"
         "INFLX_FN void inflx_kin_point([[maybe_unused]] const double x0, [[maybe_unused]] const double x1, [[maybe_unused]] const double xd0, "
+        "[[maybe_unused]] const double xd1, [[maybe_unused]] const double* __restrict__ args, double* __restrict__ o) {\n"
+        + "\n".join(lines)
+        + "\n}\n"
+    )
+
+
+def emit_masses_header(model, param_slots: dict, cse=None, cse_vector=None) -> str:
+    """The covariant Hesse matrix of the potential on a velocity and its normal, and the curvature of field space, at one point,
+    for the entropic masses (csrc/inflx_masses.h): ``inflx_mass_point(x0, x1, xd0, xd1, args, o)`` writes, with V_;ab = d_a d_b V -
+    Gamma^c_ab d_c V, xd_a = G_ab xd^b and n^b = eps^be xd_e / sqrt(det G) (the kinematics' normal times |xd|_G: n^0 = xd_1 /
+    sqrt(det G), n^1 = -xd_0 / sqrt(det G)), ``o[0]`` = V_;ab xd^a xd^b, ``o[1]`` = V_;ab xd^a n^b, ``o[2]`` = V_;ab n^a n^b -- not
+    yet divided by |xd|^2 -- and ``o[3]`` = R, the Ricci scalar.
+
+    The three components V_;00, V_;01, V_;11 are derived here from ``model.metric`` and ``model.potential``, the connection as
+    Gamma^c_ab = adj^cs [ab, s] / det G with [ab, s] = (d_a G_sb + d_b G_sa - d_s G_ab) / 2 and adj the adjugate of the 2 x 2 metric.
+    R = 2 R_0101 / det G with R_0101 = (2 d_0 d_1 G_01 - d_0 d_0 G_11 - d_1 d_1 G_00) / 2 + adj^st ([01, s][01, t] - [00, s][11, t])
+    / det G: second derivatives of the metric and products of first-kind symbols, no derivative of an inverse.  R > 0 on a sphere.
+
+    A header of its own, read only by the masses code object (``CompilationArtifact.ensure_masses``).  Written like
+    ``emit_kinematics_header``: staged with every stage inline in one function, the model's ``cse`` setting (the Hesse components
+    with R, and the metric, each through ``cse_vector``), the velocities printed as ``xd0`` / ``xd1``; metric components that print
+    as zero are skipped and the rest added left to right."""
+    if model.dim != 2:
+        raise ValueError("the entropic masses need a two-field model")
+    x = list(model.coordinates)
+    x0, x1 = x
+    potential = sympy.sympify(model.potential)
+    g = [[sympy.sympify(model.metric[i][j]) for j in range(2)] for i in range(2)]
+    metric = [g[i][j] for i in range(2) for j in range(2)]
+    det = g[0][0] * g[1][1] - g[0][1] * g[1][0]
+    adj = [[g[1][1], -g[0][1]], [-g[1][0], g[0][0]]]
+
+    def first_kind(a, b, s):
+        return (sympy.diff(g[s][b], x[a]) + sympy.diff(g[s][a], x[b]) - sympy.diff(g[a][b], x[s])) / 2
+
+    dV = [sympy.diff(potential, c) for c in x]
+    hesse = []
+    for a, b in ((0, 0), (0, 1), (1, 1)):
+        conn = sum(adj[c][s] * first_kind(a, b, s) * dV[c] for c in range(2) for s in range(2))
+        hesse.append(sympy.diff(potential, x[a], x[b]) - conn / det)
+    riemann = (2 * sympy.diff(g[0][1], x0, x1) - sympy.diff(g[1][1], x0, x0) - sympy.diff(g[0][0], x1, x1)) / 2
+    riemann += sum(adj[s][t] * (first_kind(0, 1, s) * first_kind(0, 1, t) - first_kind(0, 0, s) * first_kind(1, 1, t)) for s in range(2) for t in range(2)) / det
+    curved = hesse + [2 * riemann / det]
+    plain = C99CodePrinter()._print_Symbol
+    names = {x0: "x0", x1: "x1"}
+    for sym in set().union(*[sympy.sympify(e).free_symbols for e in curved + metric]) - set(names):
+        names[sym] = param_slots[plain(sym)]
+    functions = [cse_vector(curved) if cse_vector is not None else ([], curved), cse_vector(metric) if cse_vector is not None else ([], metric)]
+    st = Stager(functions, x0, x1, names, staged=True)
+    lines = [ln for m in (U, R, C, P) for ln in st.lines[m]]
+    texts = list(st.outputs)
+    lines += [f"  const double h00 = {texts[0]};", f"  const double h01 = {texts[1]};", f"  const double h11 = {texts[2]};", f"  const double ricci = {texts[3]};"]
+    metric_lines, det = _lowered_velocity(texts[4:8])
+    lines += metric_lines
+    lines += [
+        "  const double rdet = sqrt(" + det + ");",
+        "  const double n0 = xl1 / rdet;",
+        "  const double n1 = -xl0 / rdet;",
+        "  o[0] = h00 * xd0 * xd0 + 2.0 * h01 * xd0 * xd1 + h11 * xd1 * xd1;",
+        "  o[1] = h00 * xd0 * n0 + h01 * (xd0 * n1 + xd1 * n0) + h11 * xd1 * n1;",
+        "  o[2] = h00 * n0 * n0 + 2.0 * h01 * n0 * n1 + h11 * n1 * n1;",
+        "  o[3] = ricci;",
+    ]
+    return (
+        "// Generated by inflatox_amd.Compiler -- do not edit.\n"
+        f"// covariant Hesse matrix on (velocity, normal) and Ricci scalar of model {model.model_name} (csrc/inflx_masses.h); needs the model's core header first\n"
+        "#pragma once\n"
+        "// o[0]: V_;ab xd^a xd^b;  o[1]: V_;ab xd^a n^b;  o[2]: V_;ab n^a n^b, n^b = eps^be xd_e / sqrt(det G);  o[3]: Ricci scalar\n"
+        "INFLX_FN void inflx_mass_point([[maybe_unused]] const double x0, [[maybe_unused]] const double x1, [[maybe_unused]] const double xd0, "
         "[[maybe_unused]] const double xd1, [[maybe_unused]] const double* __restrict__ args, double* __restrict__ o) {\n"
         + "\n".join(lines)
         + "\n}\n"

@@ -22,6 +22,9 @@ time of whole calls, each ending in a stream synchronise, and the ``inflx_kin_st
 ``rocprofv3`` -- beside a device-to-device copy that moves as many bytes as the kernel reads plus writes, timed with device
 events in the same process; and the worst ratio of |result - 40-digit truth| to the allowance of tests/kinematics_reference.py
 over the zoo of tests/background_truth.py, for the host build and for the GPU.  Writes ``profiles/background_kinematics.json``.
+``--masses`` does the same for ``background.masses`` on hyperbolic and on EGNO: the ``inflx_mass_states`` kernel beside
+``inflx_kin_states`` on the same states and beside the copy, one trace of a child process per model, and the accuracy against
+tests/masses_reference.py.  Writes ``profiles/background_masses.json``.
 Run from the repository root on the GPU box.
 """
 
@@ -130,9 +133,9 @@ def sampled(log2_lanes=17, n_samples=256, rows=256, substeps=4, repeats=3, seed=
         json.dump(rec, fh, indent=1)
 
 
-def _rows_batch(log2_lanes, seed=0):
-    spec, art = workloads.artifact_for("hyperbolic")
-    (a0, b0), (a1, b1), vel = START["hyperbolic"]
+def _rows_batch(log2_lanes, seed=0, name="hyperbolic"):
+    spec, art = workloads.artifact_for(name)
+    (a0, b0), (a1, b1), vel = START[name]
     B = 1 << log2_lanes
     rng = np.random.default_rng(seed)
     x = np.stack([rng.uniform(a0, b0, B), rng.uniform(a1, b1, B)], axis=1)
@@ -250,12 +253,13 @@ COPY_KERNEL = "__amd_rocclr_copyBuffer"  # what the HIP runtime carries a device
 KIN_SETS = 3  # input sets used in turn: 3 x 201 MB read and 201 MB written per call -- a line is long out of the 256 MiB Infinity Cache when its set comes round again
 
 
-def _kinematics_rows():
-    """(artefact, parameter row, KIN_SETS views (2^14, 256, 5) of (2^14, 256, 6) device rows): the first rows of 2^14 hyperbolic
-    trajectories, repeated along the row axis with a small shift per row and per set so that no two states are the same"""
+def _kinematics_rows(name="hyperbolic"):
+    """(artefact, parameter row, KIN_SETS views (2^14, 256, 5) of (2^14, 256, 6) device rows): the first rows of 2^14 trajectories of
+    the model (hyperbolic unless named), repeated along the row axis with a small shift per row and per set so that no two states
+    are the same"""
     import torch
 
-    spec, art, x, v = _rows_batch(KIN_LOG2_TRAJ)
+    spec, art, x, v = _rows_batch(KIN_LOG2_TRAJ, name=name)
     sol = background.solve_eom_batch_device(art, spec.args, 2, x, v)
     first = torch.cat([sol.states[:, :1], sol.N[:, :1, None]], dim=2)  # (B, 1, 6)
     sets = []
@@ -265,13 +269,14 @@ def _kinematics_rows():
     return spec, art, sets
 
 
-def _copy_buffers(sets):
-    """(KIN_SETS sources, one destination) for the device-to-device copy that moves what one kinematics call moves: the call reads
-    the lines of (n, 6) rows and writes six planes, 96 bytes per state; a copy of 48 bytes per state reads and writes as much"""
+def _copy_buffers(sets, planes=6):
+    """(KIN_SETS sources, one destination) for the device-to-device copy that moves what one call moves: a kinematics call reads
+    the lines of (n, 6) rows and writes six planes, 96 bytes per state; a copy of 48 bytes per state reads and writes as much.  With
+    ``planes`` = 8, a masses call: 112 bytes per state, a copy of 56"""
     import torch
 
     n = sets[0].shape[0] * sets[0].shape[1]
-    srcs = [torch.empty(n * 6, dtype=torch.float64, device=sets[0].device).normal_() for _ in range(KIN_SETS)]
+    srcs = [torch.empty(n * (6 + planes) // 2, dtype=torch.float64, device=sets[0].device).normal_() for _ in range(KIN_SETS)]
     return srcs, torch.empty_like(srcs[0])
 
 
@@ -372,6 +377,90 @@ def kinematics_mode(repeats=8):
         fh.write("\n")
 
 
+def masses_workload(name, rounds=4):
+    """what the --masses mode runs under the profiler, once per model: a warm-up, then ``rounds`` x KIN_SETS device-resident
+    ``masses`` calls, as many ``kinematics`` calls on the same states and as many device-to-device copies of the bytes a masses call
+    moves, each over input sets used in turn"""
+    import torch
+
+    spec, art, sets = _kinematics_rows(name)
+    srcs, dst = _copy_buffers(sets, planes=8)
+    for r in range(rounds + 1):
+        for k in range(KIN_SETS):
+            mass = background.masses(art, spec.args, sets[k])
+        for k in range(KIN_SETS):
+            background.kinematics(art, spec.args, sets[k])
+        for k in range(KIN_SETS):
+            dst.copy_(srcs[k])
+        torch.cuda.synchronize()
+    print(json.dumps({"masses_workload_mu_s2_nansum": float(torch.nansum(mass.mu_s2))}), flush=True)
+
+
+def masses_accuracy():
+    """worst |result - truth| / allowance per model and quantity, host build and GPU (tests/masses_reference.py)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import background_truth as bt
+    import kinematics_reference as kr
+    import masses_reference as mr
+
+    rec = {}
+    for name in bt.GPU_MODELS:
+        states, pars = kr.zoo_states(name)
+        truth = mr.zoo_truth(name, 257)
+        host = mr.MassesTwin(bt.host_artifact(name)).masses(pars, states)
+        gpu = np.stack(background.masses(bt.device_artifact(name), pars, states))
+        allow = mr.allowance(truth, states[:, 4])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            to_host = np.where(gpu == host, 0.0, np.abs(gpu - host) / allow)
+        rec[name] = dict(host=mr.worst_ratios(host, truth, states[:, 4]), gpu=mr.worst_ratios(gpu, truth, states[:, 4]),
+                         gpu_to_host=dict(zip(mr.NAMES, (float(r) for r in to_host.max(axis=1)))))  # fmt: skip
+        print(json.dumps({name: rec[name]}), flush=True)
+    worst = {side: max(max(rec[m][side].values()) for m in rec) for side in ("host", "gpu", "gpu_to_host")}
+    return dict(states_per_model=257, allowance="tests/masses_reference.py allowance(): 1e-10 of the sum of the absolute values of the terms a quantity is built from",
+                worst=worst, models=rec)  # fmt: skip
+
+
+def masses_mode():
+    """kernel time of ``inflx_mass_states`` on 2^22 states read in place from (2^14, 256, 6) rows, hyperbolic and EGNO, beside
+    ``inflx_kin_states`` on the same states and the runtime's copy kernel moving the same bytes: one trace of a child process per
+    model, medians of the 15 dispatches of each; then the accuracy record.  Writes profiles/background_masses.json."""
+    want = KIN_SETS * 5
+    n = (1 << KIN_LOG2_TRAJ) * KIN_ROWS
+    moved = n * 6 * 8 + n * 8 * 8  # the lines of the (n, 6) rows read, the eight planes written
+    timing = {}
+    for name in ("hyperbolic", "egno"):  # first: this process has not opened the GPU yet
+        trace = _kernel_trace(KIN_LOG2_TRAJ, "--masses-workload-" + name, "", extra=("--memory-copy-trace",), each=("inflx_mass_states", "inflx_kin_states", COPY_KERNEL))
+        each = trace.get("dispatch_ns", {}) if isinstance(trace, dict) else {}
+        rec = dict(code_object=workloads.artifact_for(name)[1]._build[2])
+        for key, kernel in (("masses_kernel_s", "inflx_mass_states"), ("kinematics_kernel_s", "inflx_kin_states")):
+            rec[key] = float(np.median(each[kernel])) * 1e-9 if len(each.get(kernel, [])) == want else None
+        # (the copy kernel also serves the small uploads of the parameter row; the 15 large copies are its 15 longest dispatches)
+        rec["copy_in_trace_s"] = float(np.median(each[COPY_KERNEL][:want])) * 1e-9 if len(each.get(COPY_KERNEL, [])) >= want else None
+        if COPY_KERNEL in each:
+            each[COPY_KERNEL] = each[COPY_KERNEL][: want + 3]
+        if rec["masses_kernel_s"] and rec["copy_in_trace_s"]:
+            rec["masses_over_copy_in_trace"] = rec["masses_kernel_s"] / rec["copy_in_trace_s"]
+            rec["bytes_per_s"] = moved / rec["masses_kernel_s"]
+        if rec["masses_kernel_s"] and rec["kinematics_kernel_s"]:
+            rec["masses_over_kinematics"] = rec["masses_kernel_s"] / rec["kinematics_kernel_s"]
+        rec["trace_ns"] = trace
+        timing[name] = rec
+        print(json.dumps({name: {k: v for k, v in rec.items() if k != "trace_ns"}}), flush=True)
+    rec = dict(states=n, ld=6, traj_len=KIN_ROWS, read="plain per-lane loads (the one variant built)", input_sets=KIN_SETS, bytes_moved=moved, d2d_copy_bytes=moved // 2,
+               copy_in_trace=COPY_KERNEL, timing=timing,
+               note="per model one child process under rocprofv3 --kernel-trace that makes 15 device-resident masses calls, 15 kinematics calls on the same "
+                    "states and 15 device-to-device copies of bytes_moved / 2 bytes (a copy reads and writes each), five rounds over three input sets used in "
+                    "turn, so that what a call or a copy reads was last touched more than 1 GB of traffic earlier; masses_kernel_s, kinematics_kernel_s and "
+                    "copy_in_trace_s are the medians of the 15 dispatches of inflx_mass_states, of inflx_kin_states and of the 15 longest dispatches of the "
+                    "runtime's copy kernel, from the one trace; trace_ns.dispatch_ns: the single dispatches, longest first.  A kinematics call moves "
+                    "96 bytes per state, a masses call and the copy 112",
+               command="python scripts/background_probe.py --masses")  # fmt: skip
+    rec["accuracy"] = masses_accuracy()
+    with open(os.path.join(ROOT, "profiles", "background_masses.json"), "w") as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", action="store_true", help="time the forced host scatter, the default host call and solve_eom_batch_device (B = 2^17, 256 rows), nothing else")
@@ -382,7 +471,16 @@ def main():
     ap.add_argument("--max-log2-lanes", type=int, default=20)
     ap.add_argument("--kinematics", action="store_true", help="time background.kinematics on 2^22 device-resident states beside a device-to-device copy, and record its accuracy; nothing else")
     ap.add_argument("--kinematics-workload", action="store_true", help="a few device-resident kinematics calls (what --kinematics runs under rocprofv3)")
+    ap.add_argument("--masses", action="store_true", help="time the masses kernel on 2^22 device-resident states (hyperbolic, EGNO) beside the kinematics kernel and a device-to-device copy, and record its accuracy; nothing else")
+    ap.add_argument("--masses-workload-hyperbolic", action="store_true", help="a few device-resident masses calls on hyperbolic (what --masses runs under rocprofv3)")
+    ap.add_argument("--masses-workload-egno", action="store_true", help="the same on EGNO")
     args = ap.parse_args()
+    if args.masses_workload_hyperbolic or args.masses_workload_egno:
+        masses_workload("egno" if args.masses_workload_egno else "hyperbolic")
+        return
+    if args.masses:
+        masses_mode()
+        return
     if args.kinematics_workload:
         kinematics_workload()
         return
