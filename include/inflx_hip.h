@@ -332,6 +332,10 @@ int inflx_sf_status(inflx_model* model, unsigned* bits, int clear);
 int inflx_sf_policy(inflx_model* model, int policy);
 /* the artefact's USE_GSL global (0 / 1): Compiler(link_gsl=True), compiler.py:558, dylib.rs:135-141 */
 int inflx_uses_gsl(const inflx_model* model);
+/* 1 when the row pass of a row-only model (`<artefact>.rowpass`, CompilationArtifact.ensure_rowpass) was found beside the artefact
+ * and its broadcast sweeps evaluate their rows with it; 0 when they use the per-row kernels of the core object (slower by some
+ * microseconds per sweep, same results) or the model is not row-only */
+int inflx_has_row_pass(const inflx_model* model);
 
 /*
  * One call, several GPUs.  The reference's knob for "use the whole machine" is the `threads` argument of its sweeps:

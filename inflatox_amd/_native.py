@@ -85,6 +85,7 @@ SIGNATURES = {
     "inflx_sf_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.c_int]),
     "inflx_sf_policy": (C.c_int, [C.c_void_p, C.c_int]),
     "inflx_uses_gsl": (C.c_int, [C.c_void_p]),
+    "inflx_has_row_pass": (C.c_int, [C.c_void_p]),
     "inflx_sweep_plan": (C.c_int, [C.c_void_p, C.c_int, _SIZE, _SIZE, _SIZE, C.c_int, C.POINTER(C.c_uint32)]),
     "inflx_basis_on_points": (C.c_int, [C.c_void_p, _DP, _SIZE, _DP, _SIZE, _DP]),
     "inflx_ops_on_values": (C.c_int, [C.c_void_p, _DP, _SIZE, _DP, C.c_int]),
@@ -321,6 +322,11 @@ class InflatoxDevLib:
     def uses_gsl(self) -> bool:
         """The artefact's ``USE_GSL`` global: ``Compiler(link_gsl=True)``."""
         return bool(self._lib.inflx_uses_gsl(self._h))
+
+    @property
+    def has_row_pass(self) -> bool:
+        """The row-pass object of a row-only model (``CompilationArtifact.ensure_rowpass``) lay beside the artefact and is in use."""
+        return bool(self._lib.inflx_has_row_pass(self._h))
 
     def sf_status(self, clear: bool = True) -> int:
         """Bits (``SF_EDOM``, ``SF_EDECLINED``) the model's special functions have set since they were last cleared; waits for

@@ -336,8 +336,21 @@ class CompilationArtifact:
                      ("INFLX_MASS_HEADER", "mass{key}.h", self.masses_header_text())],
         )  # fmt: skip
 
+    def ensure_rowpass(self) -> str | None:
+        """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
+        evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
+        ".rowpass"``, which ``libinflx_hip.so`` loads with the artefact when it is there; None for every other model.  One hipcc
+        step from the core object's header and options, cached as ``<tag>.rp<hash>.hsaco`` (the hash covers ``_ROWPASS_SOURCES``,
+        code only; the tag covers the sweep kernels' source it includes); the object carries the core object's ``MODEL_TAG``.
+        ``Compiler.compile()`` calls it, so that the file exists before the artefact is first opened."""
+        if (self.stage_info or {}).get("out_mask", 3) & 2:
+            return None
+        return self._ensure_companion("rowpass", _ROWPASS_SOURCES, "rp{key}.hsaco", lambda: [])
+
     def ensure_all_groups(self) -> list[str]:
-        """Extension: every group beside the core object (what a C client of ``libinflx_hip.so`` wants in place before it starts)."""
+        """Extension: every group beside the core object (what a C client of ``libinflx_hip.so`` wants in place before it starts; the
+        row-pass object of a row-only model is there already: ``Compiler.compile()`` puts it beside the artefact, and a client that
+        copies the artefact copies ``<artefact>.rowpass`` with it -- ``inflx_has_row_pass`` tells)."""
         return [p for p in (self.ensure_group(g) for g in KERNEL_GROUPS) if p]
 
     def profile_guided(self, args, extent, silent: bool = True) -> "CompilationArtifact":
@@ -446,6 +459,7 @@ def _build_code_object(header_text: str, options: list[str], tag: str, groups: i
 _BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "inflx_background_abi.h", "inflx_background_rows.h")
 _KINEMATICS_SOURCES = ("inflx_kinematics_kernels.hip", "inflx_kinematics.h", "inflx_kinematics_abi.h")
 _MASSES_SOURCES = ("inflx_masses_kernels.hip", "inflx_masses.h", "inflx_masses_abi.h")
+_ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 
 def _build_companion_object(header_text: str, options: list[str], tag: str, sources: tuple, object_name: str, headers: list):
@@ -974,4 +988,5 @@ class Compiler:
         art.kernel_groups = self.kernel_groups
         art._build = (header, options, tag)
         art._eom_recipe = (self.symbolic_out, dict(self._param_slots), self.cse, self.max_cses)
+        art.ensure_rowpass()  # a row-only model sweeps with the row pass beside its core object (None for every other model)
         return art

@@ -40,6 +40,7 @@
 #include "inflx_background_abi.h"
 #include "inflx_background_rows.h"
 #include "inflx_kernel_abi.h"
+#include "inflx_rowpass_abi.h"
 #include "inflx_kinematics_abi.h"
 #include "inflx_masses_abi.h"
 
@@ -287,8 +288,8 @@ void prefault_range(char* begin, size_t bytes) {
   for (auto& th : pool) th.join();
 }
 
-// A double-buffered device table: one kernel writes buffer b (on the side stream, or on the caller's for a sweep enqueued alone)
-// while the kernel that reads the other buffer still runs on the caller's stream; two events per buffer order its reuse.  The
+// A double-buffered device table: one kernel writes buffer b (on the side stream, or on the caller's for a sweep that runs there
+// as a whole) while the kernel that reads the other buffer still runs on the caller's stream; two events per buffer order its reuse.  The
 // row / column table of the broadcast paths and the stage tables of the tile path are one ring each.
 struct TableRing {
   double* buf[2] = {nullptr, nullptr};
@@ -297,6 +298,11 @@ struct TableRing {
   hipEvent_t free[2] = {nullptr, nullptr};   // the kernel that last read buffer b finished
   bool used[2] = {false, false};
   unsigned turn = 0;
+  // Single-batch broadcast sweeps run both kernels on the caller's stream and record nothing: stream order is their ordering.
+  // `solo[b]` is the stream on which the last of them used buffer b (NULL: a two-stream sweep did, or nobody); a sweep that takes
+  // the buffer on another stream is first ordered behind it with `solo_done` (order_behind_solo).
+  hipStream_t solo[2] = {nullptr, nullptr};
+  hipEvent_t solo_done = nullptr;
 
   bool create() {
     // ordering-only events between two streams of this device: no system-scope fence needed (the kernels' own agent-scope
@@ -305,7 +311,7 @@ struct TableRing {
       if (hipEventCreateWithFlags(&ready[b], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
           hipEventCreateWithFlags(&free[b], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess)
         return false;
-    return true;
+    return hipEventCreateWithFlags(&solo_done, hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
   }
   void destroy() {
     for (int b = 0; b < 2; ++b) {
@@ -313,6 +319,24 @@ struct TableRing {
       if (free[b]) (void)hipEventDestroy(free[b]);
       if (buf[b]) (void)hipFree(buf[b]);
     }
+    if (solo_done) (void)hipEventDestroy(solo_done);
+  }
+  // The single-batch sweep that used buffer b last, on solo[b], comes before what `next` gets from here on.  The event is recorded
+  // now, on the earlier stream, behind everything it holds -- the sweeps themselves carry none, and a scan that stays on one stream
+  // never gets here.  That stream is the caller's: a caller must not destroy a stream while sweeps it enqueued there are still
+  // queued or running -- the handle cannot tell a reused stream handle from the old one.  A handle HIP rejects outright
+  // belongs to a stream that was destroyed after its work: the device is drained instead, which is always safe.
+  int order_behind_solo(int b, hipStream_t next) {
+    const hipStream_t last = solo[b];
+    solo[b] = nullptr;
+    if (!last || last == next) return INFLX_OK;
+    if (hipEventRecord(solo_done, last) == hipSuccess) {
+      HIP_TRY(hipStreamWaitEvent(next, solo_done, 0));
+    } else {
+      (void)hipGetLastError();
+      HIP_TRY(hipDeviceSynchronize());
+    }
+    return INFLX_OK;
   }
   // has every kernel that read one of the buffers finished?
   bool idle() const {
@@ -355,6 +379,11 @@ struct inflx_model {
   hipFunction_t rowvals[INFLX_OP_COUNT] = {};
   hipFunction_t rowstream6 = nullptr;
   hipFunction_t rowstream_planes = nullptr;
+  // the row pass of a row-only model (csrc/inflx_rowpass_kernels.hip), from `<artefact>.rowpass` when that file lies beside the
+  // artefact: takes the place of rowvals[] / rowvals_stats.  A bare core object sweeps with its own rowvals kernels.
+  hipModule_t rowpass_module = nullptr;
+  hipFunction_t rowpass[INFLX_OP_COUNT] = {};
+  hipFunction_t rowpass_stats = nullptr;
   hipFunction_t colvals[INFLX_OP_COUNT] = {};  // column-broadcast path: one row image per launch ...
   hipFunction_t colstream = nullptr;           // ... copied into every grid row
   hipFunction_t colvals_stats = nullptr;
@@ -366,8 +395,8 @@ struct inflx_model {
   hipFunction_t tile_stats = nullptr, tile_stats_nostore = nullptr, rowvals_stats = nullptr;
   double* d_stats = nullptr;  // 18 x 8 bytes: min[6], max[6], count[6]
   // Row-broadcast path: per-row results [P][rows][replicas][8], double-buffered (the column-broadcast path keeps its row images
-  // in the same ring).  The per-row evaluation of sweep n runs on `side` and overlaps the store stream of sweep n-1 on the
-  // caller's stream (it needs ~25 us of latency but hardly any bandwidth); events order table reuse.
+  // in the same ring).  A sweep of one table batch evaluates it on the caller's stream in front of its store stream; in a sweep
+  // of several batches the evaluation of batch n runs on `side` under the store stream of batch n-1, and events order table reuse.
   TableRing row_ring;
   hipStream_t side = nullptr;
   // inflx_sweep_device_timed(..., dominant_only = 2): event pairs recorded around every dominant-kernel launch of the sweeps it
@@ -449,7 +478,7 @@ int read_global(inflx_model* m, const char* sym, T* dst, size_t bytes, bool exac
 
 // Put `count` doubles of parameters where kernels enqueued on `s` can read them; *d_params is the device
 // address.  A sweep re-launches with the same rows far more often than it changes them: when the current
-// slot already holds these values for this stream nothing is uploaded.
+// slot already holds these values nothing is uploaded, whichever stream they were uploaded on.
 // Ordering rule of the ring: a slot is filled on the sweep's SweepPlan::upload_stream and released (release_params) on its
 // SweepPlan::reader_stream -- the stream of the LAST kernel that reads it -- and is refilled only once that stream has passed the
 // release.  Both come out of the one plan the entry point built for the sweep.  Released on any other stream, the slot looks free
@@ -457,7 +486,11 @@ int read_global(inflx_model* m, const char* sym, T* dst, size_t bytes, bool exac
 // call's parameters.
 int acquire_params(inflx_model* m, const double* p, size_t count, hipStream_t s, const double** d_params) {
   inflx_model::ParamSlot& cur = m->pslot[m->pcur];
-  if (cur.dev && cur.count == count && cur.stream == s && memcmp(cur.host, p, count * sizeof(double)) == 0) {
+  if (cur.dev && cur.count == count && memcmp(cur.host, p, count * sizeof(double)) == 0) {
+    // The bytes are resident (or their copy is queued on cur.stream): another stream reads them behind the slot's own event, which
+    // stands behind a reader that ran behind the copy -- nothing is uploaded twice because the stream changed.  A slot that was
+    // never released (a host-result call waits for its streams instead) has no kernel in flight, and its copy has run.
+    if (cur.stream != s && cur.in_flight) HIP_TRY(hipStreamWaitEvent(s, cur.last_use, 0));
     *d_params = cur.dev;
     return INFLX_OK;
   }
@@ -508,6 +541,18 @@ int release_params_after(inflx_model* m, hipStream_t reader, int rc) {
   (void)release_params(m, reader);
   g_last_error = first;
   return rc;
+}
+
+// A sweep whose plan carries the parameters in the kernel arguments (SweepPlan::inline_params) needs no slot: nothing to acquire,
+// nothing to release.
+template <typename Plan>
+int acquire_params_for(inflx_model* m, const Plan& plan, const double* p, size_t count, hipStream_t s, const double** d_params) {
+  *d_params = nullptr;
+  return plan.inline_params ? INFLX_OK : acquire_params(m, p, count, plan.upload_stream(m, s), d_params);
+}
+template <typename Plan>
+int release_params_for(inflx_model* m, const Plan& plan, hipStream_t s, int rc) {
+  return plan.inline_params ? rc : release_params_after(m, plan.reader_stream(m, s), rc);
 }
 
 // ---- special-function status ------------------------------------------------------------------------------------------------
@@ -616,6 +661,46 @@ int read_global_of(hipModule_t module, const char* path, const char* sym, T* dst
   return INFLX_OK;
 }
 
+// Load `<artefact>.rowpass` beside the core object of a row-only model, if the file is there (Compiler.compile() puts it there): it
+// must carry the core object's MODEL_TAG.  Without the file the handle keeps the rowvals kernels of the core object.
+int load_rowpass(inflx_model* m) {
+  const std::string path = m->path + ".rowpass";
+  FILE* fh = fopen(path.c_str(), "rb");
+  if (!fh) return INFLX_OK;
+  fclose(fh);
+  hipModule_t module = nullptr;
+  hipError_t e = hipModuleLoad(&module, path.c_str());
+  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
+  auto bail = [&](int code) {
+    const std::string first = g_last_error;
+    (void)hipModuleUnload(module);
+    g_last_error = first;
+    return code;
+  };
+  uint32_t abi = 0;
+  char tag[128] = {0};
+  int rc;
+  if ((rc = read_global_of(module, path.c_str(), "INFLX_ROWPASS_ABI", &abi, sizeof abi, true)) ||
+      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
+    return bail(rc);
+  if (abi != INFLX_ROWPASS_ABI_VERSION || m->tag != tag)
+    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another ABI (tag \"%s\", expected \"%s\")",
+                     path.c_str(), m->path.c_str(), tag, m->tag.c_str()));
+  hipFunction_t fn[INFLX_OP_COUNT] = {}, stats = nullptr;
+  for (int op = 0; op < INFLX_OP_COUNT; ++op) {
+    if (op == INFLX_OP_QDIF) continue;  // (the flag sweep never takes a broadcast path)
+    const std::string name = std::string("inflx_rowpass_") + kOpNames[op];
+    if (hipModuleGetFunction(&fn[op], module, name.c_str()) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), name.c_str()));
+  }
+  if (hipModuleGetFunction(&stats, module, "inflx_rowpass_complete_stats") != hipSuccess)
+    return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_rowpass_complete_stats", path.c_str()));
+  m->rowpass_module = module;
+  for (int op = 0; op < INFLX_OP_COUNT; ++op) m->rowpass[op] = fn[op];
+  m->rowpass_stats = stats;
+  note_sf_word(m, module);
+  return INFLX_OK;
+}
+
 // Load the code object at `path` beside the core object of `m`: it must be built from the same generated model with the same options
 // (MODEL_TAG) for the same kernel ABI; the kernels of the groups it carries and the handle lacks become available.
 int attach_object(inflx_model* m, const char* path) {
@@ -700,8 +785,12 @@ struct SweepPlan {
   size_t rows_per_launch = 0;  // tile path: grid rows per launch (at most 65535 tiles, grid.y)
   // The whole sweep runs on the caller's stream: its tables (per-row / per-column values, stage tables) are evaluated there, in
   // front of the kernel that reads them -- no second stream, no event between the two.  Otherwise they are evaluated on the side
-  // stream, under the kernels of the launch before.
+  // stream, under the kernels of the launch before.  Broadcast paths: every sweep that is a single table batch (the evaluation is
+  // 4 us in line, less than the hop between two streams costs); tile path: a single launch at an idle handle.
   bool one_stream = false;
+  // Row-broadcast path with the row-pass object loaded, single batch, at most INFLX_INLINE_PARAMS doubles: the parameter rows
+  // travel in the kernel arguments of the evaluation -- no parameter slot, no upload, no release event (plan_call sets it).
+  bool inline_params = false;
 
   // The stream the parameters are uploaded on = the stream of the first kernel that reads them: the table evaluation of the
   // broadcast and tile paths; the fallback row kernel of row-only models reads them on the caller's stream `s`.
@@ -716,12 +805,14 @@ struct SweepPlan {
   }
 };
 
-// `alone`: the sweep is enqueued on its own at a handle that has nothing running (a host-result call that is one launch + one
-// copy, a device-result call at an idle handle).  Such a sweep has nothing to overlap its table evaluation with, and the hop
-// between two streams (event record, wait, a second doorbell) is 10-15 us of the ~60 us a small sweep takes: if it is a single
-// pair of launches, both run on the caller's stream.  Sweeps that are enqueued back to back -- the chunk pipeline, the timed
-// repetitions, a call that arrives while its predecessor runs -- keep the tables on the side stream, where the table kernel of
-// sweep k+1 overlaps the dominant kernel of sweep k like the launches of a multi-launch sweep do.
+// `alone`: the sweep has nothing worth overlapping its table evaluation with: if it is a single pair of launches, both run on the
+// caller's stream, and the hop between two streams (event record, wait, a second doorbell: 10-15 us) is saved.
+//  * Tile path: a sweep enqueued on its own at a handle that has nothing running (a host-result call that is one launch + one copy,
+//    a device-result call at an idle handle).  Tile sweeps that are enqueued back to back -- the chunk pipeline, the timed
+//    repetitions, a call that arrives while its predecessor runs -- keep the tables on the side stream, where the table kernel of
+//    sweep k+1 overlaps the dominant kernel of sweep k like the launches of a multi-launch sweep do.
+//  * Broadcast paths: every sweep (plan_call) -- the evaluation takes 4 us in line, less than the hop costs, so a
+//    single table batch always runs on the caller's stream and only several batches take the double-buffered side stream.
 SweepPlan plan_sweep(const InflxKernelInfo& info, int op, int layout, size_t P, size_t N1, size_t row_count, unsigned flags, bool alone) {
   SweepPlan pl;
   const size_t K = kOpWidth[op];
@@ -770,9 +861,19 @@ SweepPlan plan_sweep(const InflxKernelInfo& info, int op, int layout, size_t P, 
   return pl;
 }
 
-// Has every kernel this handle enqueued earlier finished?  A sweep that arrives at an idle handle is planned as `alone`
-// (plan_sweep); one that arrives while the previous sweep's kernels are still running keeps the side stream, where its tables are
-// evaluated under them.  (A user's lone call and the back-to-back calls of a scan both get the shorter of the two shapes.)
+// The plan the entry points enqueue with: planned as `alone` (plan_sweep) -- the broadcast paths never ask whether the handle is
+// idle -- and a tile sweep that is not (`tile_alone` false) keeps its tables on the side stream, which is all `alone` decides.
+SweepPlan plan_call(const inflx_model* m, int op, int layout, size_t P, size_t N1, size_t row_count, unsigned flags, bool tile_alone) {
+  SweepPlan pl = plan_sweep(m->info, op, layout, P, N1, row_count, flags, /*alone=*/true);
+  if (pl.path == INFLX_PATH_TILE && !tile_alone) pl.one_stream = false;
+  // the row pass takes its parameters from its own arguments (inflx_rowpass_abi.h)
+  pl.inline_params = pl.path == INFLX_PATH_ROW_STREAM && pl.one_stream && m->rowpass_module && P * m->n_par <= INFLX_INLINE_PARAMS;
+  return pl;
+}
+
+// Has every two-stream sweep this handle enqueued earlier finished?  A tile sweep that arrives at an idle handle is planned as
+// `alone` (plan_sweep); one that arrives while the previous sweep's kernels are still running keeps the side stream, where its
+// tables are evaluated under them.  (A user's lone call and the back-to-back calls of a scan both get the shorter of the two shapes.)
 bool handle_idle(inflx_model* m) {
   const bool idle = m->row_ring.idle() && m->stage_ring.idle();
   (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure
@@ -799,27 +900,41 @@ hipError_t probe_end(inflx_model* m, hipStream_t s) {
 struct BroadcastPath {
   hipFunction_t eval;     // writes the table: per-row values / the image of one output row
   unsigned eval_gx, eval_block;
-  hipFunction_t store;    // streams the table into the result (one 16-byte store per thread, 4 KiB per workgroup)
+  bool rowpass;           // `eval` is a row-pass kernel: InflxRowPassArgs, grid.z divides the table write
+  hipFunction_t store;   // streams the table into the result (one 16-byte store per thread, 4 KiB per workgroup)
   size_t cpr;             // its workgroups per grid row
   size_t z_per_p;         // its grid.z per parameter row (planes / images)
   size_t table_doubles;   // table doubles per parameter row
 };
 
-// The broadcast paths: the table of one batch of parameter rows is evaluated on the side stream (on the caller's for a
-// single pair of launches enqueued alone), then the store stream runs on `s`.  `stores_only`: only the store streams, from
-// whatever the tables hold (used to time the dominant kernel on its own).
-int launch_broadcast(inflx_model* m, const SweepPlan& plan, const BroadcastPath& path, int op, InflxSweepArgs a, const double* d_params, size_t P,
-                     double* d_out, hipStream_t s, bool stores_only) {
+// The broadcast paths.  A sweep that is a single table batch (plan.one_stream) is two launches on `s`, evaluation then store
+// stream, and nothing else: no event, no wait, no second stream -- the two table buffers alternate, and stream order puts
+// evaluation k+1 behind store stream k.  Only a sweep whose stream differs from its predecessor's is ordered behind it first
+// (TableRing::order_behind_solo).  Several batches: the table of batch k+1 is evaluated on the side stream under the store stream
+// of batch k on `s`, two events per buffer.  `stores_only`: only the store streams, from whatever the tables hold (used to time
+// the dominant kernel on its own).  `p_host`: the parameter rows in host memory, for plan.inline_params.
+int launch_broadcast(inflx_model* m, const SweepPlan& plan, const BroadcastPath& path, int op, InflxSweepArgs a, const double* p_host,
+                     const double* d_params, size_t P, double* d_out, hipStream_t s, bool stores_only) {
   void* params[] = {&a};
+  InflxRowPassArgs ra;  // the row pass (path.rowpass) takes `a` and the in-line parameter rows
+  memset(&ra, 0, sizeof ra);
+  void* eval_params[] = {path.rowpass ? static_cast<void*>(&ra) : static_cast<void*>(&a)};
   TableRing& ring = m->row_ring;
-  const hipStream_t ev = plan.upload_stream(m, s);
+  const bool one = plan.one_stream;
+  const hipStream_t ev = one ? s : m->side;
   const size_t batch = plan.batch, row_count = a.row_count;
   if (path.cpr > 0x7fffffffULL) return fail(INFLX_ERR_SHAPE, "grid rows too long for one launch");
   // the timing-only mode re-runs store streams from the table of the sweep before it, and only the last
   // batch's table is still there
   if (stores_only && batch < P)
     return fail(INFLX_ERR_ARG, "dominant_only timing needs the parameter rows to fit one table batch (%zu rows here, got %zu)", batch, P);
+  if (plan.inline_params && !p_host && m->n_par) return fail(INFLX_ERR_ARG, "internal: a sweep planned with in-line parameters got none");
   const bool store = d_out != nullptr;
+  // write slices of the row pass (grid.z, csrc/inflx_rowpass_kernels.hip): up to four workgroups share a row block's table region while
+  // the launch still fits the chip in one round (256 CUs x 8 workgroups)
+  unsigned slices = 1;
+  if (path.rowpass)
+    while (slices < 4 && slices < a.table_replicas && (size_t)path.eval_gx * std::min(batch, P) * slices * 2 <= 2048) slices *= 2;
   for (size_t p0 = 0; p0 < P; p0 += batch) {
     const size_t pb = std::min(batch, P - p0);
     const int b = (int)((ring.turn + (stores_only ? 1 : 0)) & 1);  // (timing only: the buffer the sweep before it filled)
@@ -829,19 +944,30 @@ int launch_broadcast(inflx_model* m, const SweepPlan& plan, const BroadcastPath&
       const int rc = ring.grow(b, pb * path.table_doubles);
       if (rc) return rc;
     }
-    a.params = d_params + p0 * m->n_par;
+    if (plan.inline_params) {
+      a.params = nullptr;  // (a single batch: p0 == 0)
+      if (m->n_par) memcpy(ra.params_inline, p_host, pb * m->n_par * sizeof(double));
+    } else {
+      a.params = d_params + p0 * m->n_par;
+    }
     a.out = store ? d_out + p0 * row_count * a.N1 * kOpWidth[op] : nullptr;  // same offset for [P][rows][N1][K] and [P][K][rows][N1]
     a.P = (uint32_t)pb;
     a.row_table = store ? ring.buf[b] : nullptr;
     if (!stores_only) {
-      // the evaluation, as soon as the previous reader of this table is done
+      // the evaluation, as soon as the previous reader of this table is done: a two-stream sweep's left its event, a single-batch
+      // sweep's is in front of this one on `s` already unless it ran on another stream
       if (ring.used[b]) HIP_TRY(hipStreamWaitEvent(ev, ring.free[b], 0));
-      HIP_TRY(hipModuleLaunchKernel(path.eval, path.eval_gx, (unsigned)pb, 1, path.eval_block, 1, 1, 0, ev, params, nullptr));
-      if (ev != s) HIP_TRY(hipEventRecord(ring.ready[b], ev));
+      ring.used[b] = false;
+      const int rc = ring.order_behind_solo(b, ev);
+      if (rc) return rc;
+      if (one) ring.solo[b] = s;
+      ra.a = a;
+      HIP_TRY(hipModuleLaunchKernel(path.eval, path.eval_gx, (unsigned)pb, slices, path.eval_block, 1, 1, 0, ev, eval_params, nullptr));
+      if (!one) HIP_TRY(hipEventRecord(ring.ready[b], ev));
       ring.turn++;
     }
     if (store) {
-      if (ev != s) HIP_TRY(hipStreamWaitEvent(s, ring.ready[b], 0));
+      if (!one) HIP_TRY(hipStreamWaitEvent(s, ring.ready[b], 0));
       // grid.y is limited to 65535, longer slabs take several launches
       for (size_t r0 = 0; r0 < row_count; r0 += 65535) {
         a.stream_row0 = (uint32_t)r0;
@@ -850,8 +976,10 @@ int launch_broadcast(inflx_model* m, const SweepPlan& plan, const BroadcastPath&
         HIP_TRY(hipModuleLaunchKernel(path.store, (unsigned)path.cpr, (unsigned)nr, (unsigned)(pb * path.z_per_p), m->info.tile_cols, 1, 1, 0, s, params, nullptr));
         HIP_TRY(probe_end(m, s));
       }
-      HIP_TRY(hipEventRecord(ring.free[b], s));
-      ring.used[b] = true;
+      if (!one) {
+        HIP_TRY(hipEventRecord(ring.free[b], s));
+        ring.used[b] = true;
+      }
     }
   }
   return INFLX_OK;
@@ -947,9 +1075,10 @@ int launch_tiles(inflx_model* m, const SweepPlan& plan, int op, InflxSweepArgs a
   return INFLX_OK;
 }
 
-// Enqueue one sweep on `s` the way `plan` says; `d_params` points at P parameter rows in device memory.
+// Enqueue one sweep on `s` the way `plan` says; `d_params` points at P parameter rows in device memory, `p_host` at the same rows
+// in host memory (a plan with inline_params reads those, and d_params may be NULL).
 // `stores_only`: of the two-launch broadcast paths only the store stream (used to time the dominant kernel on its own).
-int launch_grid(inflx_model* m, const SweepPlan& plan, int op, const double* d_params, size_t P, double* d_out, const double* ss, size_t N0,
+int launch_grid(inflx_model* m, const SweepPlan& plan, int op, const double* p_host, const double* d_params, size_t P, double* d_out, const double* ss, size_t N0,
                 size_t N1, size_t row_begin, size_t row_count, int layout, hipStream_t s, bool stores_only = false, double accuracy = 0.0,
                 double* d_stats = nullptr) {
   if (row_count == 0 || N1 == 0) return INFLX_OK;
@@ -959,7 +1088,7 @@ int launch_grid(inflx_model* m, const SweepPlan& plan, int op, const double* d_p
     for (size_t p0 = 0; p0 < P; p0 += 65535) {
       const size_t pb = std::min<size_t>(65535, P - p0);
       double* sub = d_out ? reinterpret_cast<double*>(reinterpret_cast<char*>(d_out) + p0 * row_count * N1 * kOpBytes[op]) : nullptr;
-      const int rc = launch_grid(m, plan, op, d_params + p0 * m->n_par, pb, sub, ss, N0, N1, row_begin, row_count, layout, s, stores_only, accuracy, d_stats);
+      const int rc = launch_grid(m, plan, op, p_host + p0 * m->n_par, d_params + p0 * m->n_par, pb, sub, ss, N0, N1, row_begin, row_count, layout, s, stores_only, accuracy, d_stats);
       if (rc) return rc;
     }
     return INFLX_OK;
@@ -988,18 +1117,20 @@ int launch_grid(inflx_model* m, const SweepPlan& plan, int op, const double* d_p
       const bool aos6 = K == 6 && layout == INFLX_AOS;
       a.table_replicas = (uint32_t)plan.replicas;
       a.stream_planes = (uint32_t)K;
-      const BroadcastPath path = {d_stats ? m->rowvals_stats : m->rowvals[op], (unsigned)((row_count + 63) / 64), 64,
+      const bool rp = m->rowpass_module != nullptr;  // (else the core object's own evaluation: one wavefront per 64 rows)
+      const BroadcastPath path = {d_stats ? (rp ? m->rowpass_stats : m->rowvals_stats) : (rp ? m->rowpass[op] : m->rowvals[op]), (unsigned)((row_count + 63) / 64),
+                                  rp ? (unsigned)m->info.tile_cols : 64u, rp,
                                   aos6 ? m->rowstream6 : m->rowstream_planes, plan.cpr, aos6 ? 1 : K, row_count * plan.replicas * 8};
-      return launch_broadcast(m, plan, path, op, a, d_params, P, d_out, s, stores_only);
+      return launch_broadcast(m, plan, path, op, a, p_host, d_params, P, d_out, s, stores_only);
     }
     case INFLX_PATH_COL_STREAM: {
       // the image of one output row per parameter row (and plane) into the table, then the copy stream
       const bool planes = layout == INFLX_SOA || K == 1;
       a.stream_units = (planes ? N1 : K * N1) / 2;  // 16-byte units per output row
       const size_t tc = m->info.tile_cols;
-      const BroadcastPath path = {d_stats ? m->colvals_stats : m->colvals[op], (unsigned)((N1 + tc - 1) / tc), (unsigned)tc,
+      const BroadcastPath path = {d_stats ? m->colvals_stats : m->colvals[op], (unsigned)((N1 + tc - 1) / tc), (unsigned)tc, false,
                                   m->colstream, (a.stream_units + tc - 1) / tc, planes ? K : 1, K * N1};
-      return launch_broadcast(m, plan, path, op, a, d_params, P, d_out, s, stores_only);
+      return launch_broadcast(m, plan, path, op, a, p_host, d_params, P, d_out, s, stores_only);
     }
     case INFLX_PATH_ROWS:
       return launch_rows_fallback(m, op, a, P, N1, row_count, s);
@@ -1183,6 +1314,7 @@ int inflx_open(const char* artefact_path, int device, inflx_model** out) {
     if ((rc = resolve_group_kernels(m, m->module, present, artefact_path))) return bail(rc);
     m->groups = present;
   }
+  if ((m->info.out_mask & 2u) == 0 && (rc = load_rowpass(m))) return bail(rc);
   if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1238,6 +1370,7 @@ void inflx_close(inflx_model* m) {
   if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
   for (hipModule_t extra : m->attached) (void)hipModuleUnload(extra);
   if (m->bg_module) (void)hipModuleUnload(m->bg_module);
+  if (m->rowpass_module) (void)hipModuleUnload(m->rowpass_module);
   if (m->kin_module) (void)hipModuleUnload(m->kin_module);
   if (m->mass_module) (void)hipModuleUnload(m->mass_module);
   if (m->module) (void)hipModuleUnload(m->module);
@@ -1318,9 +1451,9 @@ int inflx_sweep_device_stats(inflx_model* m, const double* p, size_t P, size_t n
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
   // `up`: the stream of the first kernel of the sweep (parameters and the initial summary are ordered before it);
-  // `eval`: the stream of the kernels that accumulate (the per-row / per-column evaluation of the broadcast paths on the
-  // side stream, the tile kernels on the caller's)
-  const SweepPlan plan = plan_sweep(m->info, op, INFLX_AOS, P, N1, row_count, INFLX_SWEEP_DEFAULT, /*alone=*/false);
+  // `eval`: the stream of the kernels that accumulate (the per-row / per-column evaluation of the broadcast paths -- on the
+  // caller's stream for a single table batch, on the side stream for several --, the tile kernels on the caller's)
+  const SweepPlan plan = plan_call(m, op, INFLX_AOS, P, N1, row_count, INFLX_SWEEP_DEFAULT, /*tile_alone=*/false);
   hipStream_t up = plan.upload_stream(m, s), eval = plan.reader_stream(m, s);
   if (!m->d_stats) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_stats), 18 * sizeof(double)));
   inflx_summary init;
@@ -1332,11 +1465,11 @@ int inflx_sweep_device_stats(inflx_model* m, const double* p, size_t P, size_t n
   static_assert(sizeof(inflx_summary) == 18 * 8, "inflx_summary must match the device layout");
   HIP_TRY(hipMemcpyAsync(m->d_stats, &init, sizeof init, hipMemcpyHostToDevice, up));
   const double* d_params = nullptr;
-  if ((rc = acquire_params(m, p, P * n_p, up, &d_params))) return rc;
+  if ((rc = acquire_params_for(m, plan, p, P * n_p, s, &d_params))) return rc;
   if (row_count && N1) {
-    rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, INFLX_AOS, s, false, 0.0, m->d_stats);
+    rc = launch_grid(m, plan, op, p, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, INFLX_AOS, s, false, 0.0, m->d_stats);
   }
-  if ((rc = release_params_after(m, eval, rc))) return rc;
+  if ((rc = release_params_for(m, plan, s, rc))) return rc;
   HIP_TRY(hipMemcpyAsync(summary, m->d_stats, sizeof *summary, hipMemcpyDeviceToHost, eval));
   HIP_TRY(hipStreamSynchronize(eval));
   if (eval != s) HIP_TRY(hipStreamSynchronize(s));
@@ -1368,6 +1501,8 @@ int inflx_sf_policy(inflx_model* m, int policy) {
 
 int inflx_uses_gsl(const inflx_model* m) { return m ? (int)m->use_gsl : 0; }
 
+int inflx_has_row_pass(const inflx_model* m) { return m && m->rowpass_module ? 1 : 0; }
+
 int inflx_sweep_device(inflx_model* m, int op, const double* p, size_t P, size_t n_p, void* d_out, size_t d_out_bytes,
                        const double* ss, size_t N0, size_t N1, size_t row_begin, size_t row_count, int layout, void* stream) {
   return inflx_sweep_device_ex(m, op, p, P, n_p, d_out, d_out_bytes, ss, N0, N1, row_begin, row_count, layout, stream, INFLX_SWEEP_DEFAULT);
@@ -1387,13 +1522,15 @@ int inflx_sweep_device_ex(inflx_model* m, int op, const double* p, size_t P, siz
   if (d_out_bytes < need) return fail(INFLX_ERR_SHAPE, "output buffer has %zu bytes, the sweep writes %zu", d_out_bytes, need);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
-  // the parameters are read by the kernel that evaluates the model: the per-row / per-column evaluation or the stage tables -- on the
-  // side stream while an earlier sweep of this handle is still running (they overlap it), on the caller's stream at an idle handle
-  const SweepPlan plan = plan_sweep(m->info, op, layout, P, N1, row_count, flags, /*alone=*/handle_idle(m));
+  // the parameters are read by the kernel that evaluates the model: the per-row / per-column evaluation (single batch: from its own
+  // arguments, on the caller's stream) or the stage tables -- on the side stream while an earlier tile sweep of this handle is still
+  // running (they overlap it), on the caller's stream at an idle handle
+  SweepPlan plan = plan_call(m, op, layout, P, N1, row_count, flags, /*tile_alone=*/true);
+  if (plan.path == INFLX_PATH_TILE && plan.one_stream && !handle_idle(m)) plan.one_stream = false;  // (asked only where it matters)
   const double* d_params = nullptr;
-  if ((rc = acquire_params(m, p, P * n_p, plan.upload_stream(m, s), &d_params))) return rc;
-  rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s);
-  rc = release_params_after(m, plan.reader_stream(m, s), rc);
+  if ((rc = acquire_params_for(m, plan, p, P * n_p, s, &d_params))) return rc;
+  rc = launch_grid(m, plan, op, p, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s);
+  rc = release_params_for(m, plan, s, rc);
   if (rc == INFLX_OK && !m->sf_words.empty() && s != m->stream) {  // (see sf_done: the stream that finishes the sweep is the caller's)
     if (!m->sf_done) HIP_TRY(hipEventCreateWithFlags(&m->sf_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(m->sf_done, s));
@@ -1440,12 +1577,11 @@ int inflx_sweep_device_timed_ex(inflx_model* m, int op, const double* p, size_t 
     return INFLX_OK;
   }
   const int dominant_only = mode;
-  const double* d_params = m->pslot[m->pcur].dev;  // what the call above uploaded (or found in place)
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(m->side));
-  // the repetitions are enqueued back to back: the shape of a sweep that arrives while its predecessor runs (tables on the side stream)
-  const SweepPlan plan = plan_sweep(m->info, op, layout, P, N1, row_count, flags, /*alone=*/false);
-  const hipStream_t reader = plan.reader_stream(m, s);
+  // the repetitions are enqueued back to back: the shape of a sweep that arrives while its predecessor runs (tile path: tables on the side stream)
+  const SweepPlan plan = plan_call(m, op, layout, P, N1, row_count, flags, /*tile_alone=*/false);
+  const double* d_params = plan.inline_params ? nullptr : m->pslot[m->pcur].dev;  // what the call above uploaded (or found in place)
   // dominant_only == 2: the full sweeps, with an event pair around every dominant-kernel launch (at most 64 per sweep)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;
   struct Disarm {
@@ -1471,12 +1607,12 @@ int inflx_sweep_device_timed_ex(inflx_model* m, int op, const double* p, size_t 
   }
   HIP_TRY(hipEventRecord(m->t0, s));
   for (int k = 0; k < repeats; ++k) {
-    rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s,
+    rc = launch_grid(m, plan, op, p, d_params, P, static_cast<double*>(d_out), ss, N0, N1, row_begin, row_count, layout, s,
                      /*stores_only=*/dominant_only == 1);
-    if (rc) return release_params_after(m, reader, rc);
+    if (rc) return release_params_for(m, plan, s, rc);
   }
   HIP_TRY(hipEventRecord(m->t1, s));
-  if ((rc = release_params(m, reader))) return rc;
+  if ((rc = release_params_for(m, plan, s, INFLX_OK))) return rc;
   HIP_TRY(hipEventSynchronize(m->t1));
   float ms = 0.f;
   if (dominant_only == 2) {
@@ -1856,15 +1992,15 @@ int sweep_host_body(inflx_model* m, int op, const double* p, size_t P, size_t n_
   }
   // planned with the P the launches below really see (the whole-result path launches all P rows at once, the chunk pipeline one
   // parameter row at a time, back to back); both paths wait for their streams before they return, so the slot needs no release
-  const SweepPlan plan = plan_sweep(m->info, op, layout, whole ? P : 1, N1, row_count, INFLX_SWEEP_DEFAULT, /*alone=*/whole);
+  const SweepPlan plan = plan_call(m, op, layout, whole ? P : 1, N1, row_count, INFLX_SWEEP_DEFAULT, /*tile_alone=*/whole);
   const double* d_params = nullptr;
-  if ((rc = acquire_params(m, p, P * n_p, plan.upload_stream(m, m->stream), &d_params))) return rc;
+  if ((rc = acquire_params_for(m, plan, p, P * n_p, m->stream, &d_params))) return rc;
   if (whole) {
     // One launch for everything, and as few copies as the destination allows (one when the caller's array is the slab):
     // the device buffer has the layout of the slab.  The destination pages are made resident by helper threads that run
     // ahead of the copy: the first stretch before the copy starts, the rest -- in stripes dealt round-robin, so that the
     // resident frontier advances at the aggregate rate, several times the PCIe rate -- while it is under way.
-    rc = launch_grid(m, plan, op, d_params, P, static_cast<double*>(m->d_whole), ss, N0, N1, row_begin, row_count, layout, m->stream, false, accuracy);
+    rc = launch_grid(m, plan, op, p, d_params, P, static_cast<double*>(m->d_whole), ss, N0, N1, row_begin, row_count, layout, m->stream, false, accuracy);
     if (rc) {  // kernels enqueued before the failure may still read the parameter slot
       (void)hipStreamSynchronize(m->side);
       (void)hipStreamSynchronize(m->stream);
@@ -2017,7 +2153,7 @@ int sweep_host_body(inflx_model* m, int op, const double* p, size_t P, size_t n_
       if (progress)
         for (; counted + 2 <= c; ++counted) progress->done += pieces[counted].nrows * piece_row_bytes;
     }
-    rc = launch_grid(m, plan, op, d_params + pc.pr * n_p, 1, static_cast<double*>(m->d_chunk[b]), ss, N0, N1, row_begin + pc.r, pc.nrows, layout,
+    rc = launch_grid(m, plan, op, p + pc.pr * n_p, d_params ? d_params + pc.pr * n_p : nullptr, 1, static_cast<double*>(m->d_chunk[b]), ss, N0, N1, row_begin + pc.r, pc.nrows, layout,
                      m->stream, false, accuracy);
     if (rc) { drain(); return rc; }
     if (ready.valid()) ready.wait();  // pages of this chunk's destination are resident
