@@ -584,6 +584,41 @@ int inflx_masses(inflx_model* model, const double* p, size_t P, size_t n_p, cons
 int inflx_masses_device(inflx_model* model, const double* p, size_t P, size_t n_p, const void* d_states, size_t d_states_bytes, size_t n, size_t ld,
                         size_t traj_len, void* d_out, size_t d_out_bytes, void* stream);
 
+/*
+ * Super-horizon transfer functions of B trajectories (csrc/inflx_transfer.h): the background of inflx_solve_eom_sampled and, carried
+ * along it from the initial state (horizon exit), the entropic perturbation q = Q_s / Q_s(0) and the curvature perturbation it
+ * sources.  With kin, cross and m[.] as for inflx_kinematics and inflx_masses, Omega = cross / kin = omega H, eps = kin / (2 H^2):
+ *   dq/dt = u      du/dt = -3 H u - H^2 mu_s2 q      dr/dt = 2 Omega q sqrt(eps_star / eps)      (q, u, r)(0) = (1, H0 dq_dN, 0)
+ * T_SS = q sqrt(eps_star / eps) = S / S_star with S = Q_s / sqrt(2 eps), and T_RS = r: R(N) = R_star + T_RS S_star.  Q_s is measured
+ * along T turned COUNTER-CLOCKWISE in the chart -- minus the N of inflx_kinematics, the side the trajectory turns towards when
+ * omega > 0 --, so that dR/dN = +2 omega S with the signed omega of inflx_kinematics.
+ *   p, P, n_p, init, B, method, dt    as for inflx_solve_eom
+ *   dq_dn      (B,) finite: dq/dN at the start -- or NULL: the slowly decaying root of lambda^2 + (3 - eps_star) lambda + mu_s2_star
+ *              = 0 (its real part when the discriminant is negative), from the model at every lane's initial state
+ *   samples    (S,): e-fold counts since the start; finite, >= 0, strictly increasing; 1 <= S < 2^32
+ *   max_steps  accepted steps a trajectory may take
+ *   max_err    error bound of the adaptive step: the absolute Euclidean norm over phi, chi, H, q, u and r (eight components), so an
+ *              adaptive run takes other steps than inflx_solve_eom_sampled; with dt > 0 the background is that call's bit for bit
+ *   flags      INFLX_EOM_STOP_AT_END
+ *   out        (S, 10, B), trajectory fastest: phi^0, phi^1, chi^0, chi^1, H, N, t, epsilon_H, T_SS, T_RS at every sample, located
+ *              as inflx_solve_eom_sampled locates them (q and r by the same cubic Hermite interpolant); NaN for a sample that the
+ *              trajectory did not reach.  A sample at 0 has T_SS = 1 and T_RS = 0 exactly
+ *   ends       (B, 2): T_SS and T_RS at epsilon_H = 1, linear across the step that ends inflation at N_end's own fraction of it;
+ *              meaningful for INFLX_EOM_ENDED (NaN otherwise)
+ *   efolds, status, n_stored    as for inflx_solve_eom_sampled, except that a sample emitted by the initial state (N = 0) never
+ *              stops a lane: INFLX_EOM_TARGET comes from the step that emits the last sample, and samples = {0} runs on to the
+ *              end of inflation or max_steps.  A lane whose initial state has kin = 0, or whose eps_star,
+ *              omega_star or mu_s2_star is not finite, is INFLX_EOM_NONFINITE at once and all its outputs are NaN
+ * `ends`, `efolds` and `n_stored` may be NULL.  The object `<artefact>.transfer` (CompilationArtifact.ensure_transfer()) is loaded on
+ * first use and must carry the artefact's MODEL_TAG and this library's layout word INFLX_TR_ABI; INFLX_ERR_SYMBOL when it does not
+ * exist, INFLX_ERR_VERSION when it belongs to another model or layout.  Arguments are checked before anything touches the device.
+ * Runs on the handle's stream in passes of at most 2^20 lanes and 2^28 bytes of samples, launches of at most 256 accepted steps,
+ * and stops launching once no trajectory runs any more.  A USE_GSL artefact follows the error policy of inflx_solve_eom.
+ */
+int inflx_transfer_functions(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* dq_dn,
+                             const double* samples, size_t S, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out,
+                             double* ends, double* efolds, int8_t* status, uint32_t* n_stored);
+
 #ifdef __cplusplus
 }
 #endif

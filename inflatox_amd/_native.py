@@ -123,6 +123,11 @@ SIGNATURES = {
     "inflx_kinematics_device": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, C.c_void_p, _SIZE, _SIZE, _SIZE, _SIZE, C.c_void_p, _SIZE, C.c_void_p]),
     "inflx_masses": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, _SIZE, _DP]),
     "inflx_masses_device": (C.c_int, [C.c_void_p, _DP, _SIZE, _SIZE, C.c_void_p, _SIZE, _SIZE, _SIZE, _SIZE, C.c_void_p, _SIZE, C.c_void_p]),
+    "inflx_transfer_functions": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, C.POINTER(C.c_int8),
+         C.POINTER(C.c_uint32)],
+    ),
 }
 
 
@@ -137,7 +142,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -591,6 +596,39 @@ class InflatoxDevLib:
                 int(d_out_bytes), C.c_void_p(stream),
             )
         )  # fmt: skip
+
+    # ---- transfer functions (include/inflx_hip.h: inflx_transfer_functions) ----------------------
+    def transfer_functions(self, p, init, dq_dn, samples, max_steps: int, method: int, max_err: float, dt: float, flags: int):
+        """B trajectories from ``init`` (B,4) with the super-horizon perturbations carried along, sampled at the e-fold counts
+        ``samples`` (S,) shared by all of them; ``dq_dn`` (B,) or None (the slowly decaying root).  Returns (out (S, 10, B): y[0..5],
+        t, epsilon_H, T_SS, T_RS at every sample, trajectory fastest; ends (B, 2): T_SS, T_RS at epsilon_H = 1; efolds; status (int8);
+        n_stored (uint32)).  ``flags``: ``EOM_STOP_AT_END`` or 0.  The transfer object must be in place
+        (``CompilationArtifact.ensure_transfer``)."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        samples = _f64(samples, "samples")
+        if samples.ndim != 1:
+            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        B, S = init.shape[0], samples.size
+        if dq_dn is not None:
+            dq_dn = _f64(dq_dn, "dq_dn")
+            if dq_dn.shape != (B,):
+                raise InflatoxShapeError(f"dq_dn must have shape ({B},) (got {dq_dn.shape})")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((S, 10, B))
+        ends = np.empty((B, 2))
+        efolds = np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        n_stored = np.empty(B, dtype=np.uint32)
+        _check(
+            self._lib.inflx_transfer_functions(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, None if dq_dn is None else _ptr(dq_dn), _ptr(samples), S, int(max_steps), int(method),
+                float(max_err), float(dt), int(flags), _ptr(out), _ptr(ends), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+                n_stored.ctypes.data_as(C.POINTER(C.c_uint32)),
+            )
+        )  # fmt: skip
+        return out, ends, efolds, status, n_stored
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

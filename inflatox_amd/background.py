@@ -13,7 +13,10 @@ these states -- host arrays, or the device-resident rows of ``solve_eom_batch_de
 ``turn_rate_map`` is ``horizon_exit_map`` followed by ``kinematics``: the measured counterpart, over the same grid, of what
 ``GeneralisedAL.complete_analysis`` predicts from the potential alone.  ``masses`` evaluates the second-order counterpart at the same
 states -- the covariant Hesse matrix on the trajectory's own tangent and normal, the Ricci scalar of field space and the two entropic
-masses built from them -- and ``mass_map`` is ``horizon_exit_map`` followed by it.
+masses built from them -- and ``mass_map`` is ``horizon_exit_map`` followed by it.  ``transfer_functions`` integrates the two
+super-horizon perturbation equations whose coefficients are that turn rate and that mass along every trajectory -- T_RS, the
+curvature perturbation sourced after horizon exit, and T_SS, the isocurvature that survives -- and ``transfer_map`` is
+``horizon_exit_map`` followed by it, from every exit state to the end of inflation.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -38,7 +41,8 @@ from ._native import InflatoxShapeError
 from .compiler import CompilationArtifact
 
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
-           "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses"]  # fmt: skip
+           "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses", "transfer_functions", "transfer_map",
+           "TransferSolution"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -553,3 +557,142 @@ def mass_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, 
     state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
     mass = masses(artifact, pars, state)
     return (mass, state, n_end, status) if return_status else (mass, state, n_end)
+
+
+class TransferSolution(NamedTuple):
+    """What :func:`transfer_functions` returns.  ``T_SS``, ``T_RS``, ``t``, ``N`` and ``eps_H`` (B, S) and ``states`` (B, S, 5): the
+    transfer functions, cosmic time, e-folds, epsilon_H and phi^0, phi^1, chi^0, chi^1, H at every sample -- all views of one
+    (S, 10, B) array, trajectory fastest, and NaN for a sample the trajectory did not reach; ``n_stored`` (B,): the samples emitted,
+    always the first ``n_stored``; ``N_end``, ``T_SS_end`` and ``T_RS_end`` (B,): N and the transfer functions at epsilon_H = 1 of a
+    trajectory that ENDED (``stop_at_end``), NaN otherwise; ``status`` (B,) int8 as for :func:`solve_eom_sampled`."""
+
+    T_SS: np.ndarray
+    T_RS: np.ndarray
+    t: np.ndarray
+    N: np.ndarray
+    eps_H: np.ndarray
+    states: np.ndarray
+    n_stored: np.ndarray
+    N_end: np.ndarray
+    T_SS_end: np.ndarray
+    T_RS_end: np.ndarray
+    status: np.ndarray
+
+
+def _check_dq_dN(dq_dN, B):
+    if dq_dN is None:
+        return None
+    try:
+        d = np.asarray(dq_dN, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("dq_dN must be None, a number or a float64 array") from None
+    if d.ndim == 0:
+        d = np.full(B, float(d))
+    if d.shape != (B,):
+        raise InflatoxShapeError(f"dq_dN must be a scalar or have shape ({B},) (got {d.shape})")
+    if not np.isfinite(d).all():
+        raise ValueError("dq_dN must be finite")
+    return np.ascontiguousarray(d)
+
+
+def transfer_functions(artifact: CompilationArtifact, pars, samples, fields_init, derivatives_init, max_steps: int = 100_000, max_err: float = 1e-8,
+                       solver: str = "rkf", *, dq_dN=None, dt: float | None = None, stop_at_end: bool = True) -> TransferSolution:  # fmt: skip
+    """The super-horizon transfer functions of B trajectories from their initial states -- horizon exit -- at every e-fold count of
+    ``samples`` (S,) since the start: finite, >= 0, strictly increasing, one list shared by all.  ``fields_init``,
+    ``derivatives_init``, ``pars``, ``solver``, ``dt``, ``max_steps`` and ``stop_at_end`` as for ``solve_eom_sampled``, and its
+    argument checks.  One GPU lane per trajectory integrates the background y = (phi, chi, H, N) together with (q, u, r), cosmic time::
+
+        dq/dt = u,   du/dt = -3 H u - H^2 mu_s2 q,   dr/dt = 2 omega H q sqrt(eps_star / eps_H),   (q, u, r)(0) = (1, H0 dq_dN, 0)
+
+    with ``omega`` the signed turn rate per e-fold of :func:`kinematics`, ``mu_s2`` the super-horizon entropic mass of :func:`masses`
+    and eps_star = eps_H at the start, all evaluated by the model inside every Runge-Kutta stage (csrc/inflx_transfer.h).  q =
+    Q_s / Q_s(0) is the entropic perturbation; ``T_SS`` = q sqrt(eps_star / eps_H) is S / S_star for S = Q_s / sqrt(2 eps_H), and
+    ``T_RS`` = r, where R(N) = R_star + T_RS S_star: 1 + T_RS^2 is the growth of the curvature power after horizon exit for
+    uncorrelated modes of equal amplitude.
+
+    Orientation and sign: Q_s is measured along T turned COUNTER-CLOCKWISE in the (phi^0, phi^1) chart.  That is minus the normal N
+    of :class:`Kinematics`, the side the trajectory turns towards when omega > 0; with it dR/dN = +2 omega S for the project's
+    signed omega.
+
+    ``dq_dN``: d ln Q_s / dN at the start, a scalar or (B,), finite.  None (the default): the slowly decaying root of
+    lambda^2 + (3 - eps_star) lambda + mu_s2_star = 0, lambda = [-(3 - eps_star) + sqrt((3 - eps_star)^2 - 4 mu_s2_star)] / 2, and its
+    real part -(3 - eps_star) / 2 when the discriminant is negative -- computed on the device from the model at every initial state.
+
+    Steps and samples: the steppers, acceptance rule and statuses are ``solve_eom_sampled``'s, but ``max_err`` bounds the absolute
+    Euclidean norm of the error over phi, chi, H, q, u and r (eight components), so an adaptive run takes OTHER steps than
+    ``solve_eom_sampled``; with a fixed ``dt`` the background (``states``, ``t``, ``N``, ``eps_H``) is that function's bit for bit.
+    Samples are located as there, q and r with the same cubic Hermite interpolant; a sample at 0 has T_SS = 1, T_RS = 0 exactly.
+    With ``stop_at_end``, in the step where epsilon_H reaches 1 only the samples up to ``N_end`` are emitted, and ``T_SS_end``,
+    ``T_RS_end`` are linear across that step at N_end's own fraction of it (a trajectory that starts past the end: 1 and 0).  A
+    trajectory stops (``TARGET``) in the step that emits its last sample; a sample at 0, which the initial state emits, never stops
+    it, so ``samples=[0.0]`` asks for the end values alone and runs to the end of inflation (``ENDED``) or ``max_steps``.  As in
+    ``solve_eom_sampled``, a step that both passes the last sample and ends inflation (the sample at or before ``N_end``) makes the
+    trajectory ``TARGET``, not ``ENDED``: its ``N_end``, ``T_SS_end`` and ``T_RS_end`` are NaN like those of every trajectory that
+    is not ``ENDED``; put a sample beyond the end of inflation (or pass ``[0.0]``) where the end values are what is wanted.  A
+    trajectory at rest at the start (no direction), or one whose eps_star, omega or mu_s2 there is not finite, is ``NONFINITE`` at
+    once with NaN everywhere.  The kernels are built into ``<artefact>.transfer`` on first use
+    (``CompilationArtifact.ensure_transfer``).  Bad arguments raise before anything runs on the device."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    try:
+        pts = np.ascontiguousarray(samples, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("samples must be convertible to a float64 array") from None
+    if pts.ndim != 1:
+        raise InflatoxShapeError(f"samples must be one-dimensional (got shape {pts.shape})")
+    if pts.size < 1 or pts.size >= 2**32:
+        raise ValueError(f"the number of samples must be in [1, 2^32) (got {pts.size})")
+    if not (np.isfinite(pts).all() and (pts >= 0.0).all()):
+        raise ValueError("samples must be finite and >= 0")
+    if not (np.diff(pts) > 0.0).all():
+        raise ValueError("samples must be strictly increasing")
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    p = _pars(artifact, pars, x.shape[0])
+    dq = _check_dq_dN(dq_dN, x.shape[0])
+    init = np.concatenate([x, v], axis=1)
+    flags = _native.EOM_STOP_AT_END if stop_at_end else 0
+    artifact.ensure_transfer()
+    lib = _dylib(artifact, background=False)
+    out, ends, n_end, status, n_stored = lib.transfer_functions(p, init, dq, pts, max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
+    ended = status == ENDED
+    return TransferSolution(out[:, 8].T, out[:, 9].T, out[:, 6].T, out[:, 5].T, out[:, 7].T, out[:, :5].transpose(2, 0, 1), n_stored,
+                            np.where(ended, n_end, np.nan), np.where(ended, ends[:, 0], np.nan), np.where(ended, ends[:, 1], np.nan), status)  # fmt: skip
+
+
+def transfer_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, derivatives_init=(0.0, 0.0),
+                 max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, dq_dN=None, return_status: bool = False):  # fmt: skip
+    """``horizon_exit_map`` (same arguments) followed by ``transfer_functions`` from every exit state to the end of inflation:
+    ``((T_RS, T_SS), state, N_end)`` with ``T_RS`` and ``T_SS`` the (N0, N1) end values ``T_RS_end`` and ``T_SS_end`` of the
+    trajectory that starts at the fields and velocities of the state ``N_star`` e-folds before the end of inflation from every grid
+    point (``samples=[0.0]``, ``stop_at_end``), and ``state`` (N0, N1, 5) and ``N_end`` (N0, N1) exactly ``horizon_exit_map``'s.  The
+    second stage takes H again from the Friedmann constraint at the exit state's fields and velocities, not the H of ``state``
+    (they differ by the integration error of the first stage).  ``dq_dN``: None, a scalar, or an (N0, N1) array with a value for
+    every grid point (finite everywhere, also where no exit state is found).  NaN
+    where no exit state was found or the second stage did not reach the end of inflation; ``return_status=True`` adds the (N0, N1)
+    status map: ``horizon_exit_map``'s, with the second stage's status (``ENDED`` where the transfer functions are valid) in place
+    of ``TARGET``."""
+    if dq_dN is not None:
+        try:
+            n_grid = operator.index(N0) * operator.index(N1)
+        except TypeError:
+            raise ValueError("N0 and N1 must be integers") from None
+        per_point = np.ndim(dq_dN) == 2
+        if per_point and np.shape(dq_dN) != (N0, N1):
+            raise InflatoxShapeError(f"dq_dN must be a scalar or have shape ({N0}, {N1}) (got {np.shape(dq_dN)})")
+        dq_dN = _check_dq_dN(np.reshape(dq_dN, -1) if per_point else dq_dN, max(n_grid, 0) if per_point else 1)
+        if not per_point:
+            dq_dN = np.full(max(n_grid, 0), dq_dN[0])
+    state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
+    N0, N1 = n_end.shape
+    flat = state.reshape(-1, 5)
+    status = status.copy().reshape(-1)
+    t_rs, t_ss = np.full(N0 * N1, np.nan), np.full(N0 * N1, np.nan)
+    run = np.flatnonzero(status == TARGET)
+    if run.size:
+        tf = transfer_functions(artifact, pars, [0.0], flat[run, :2], flat[run, 2:4], max_steps, max_err, solver, dq_dN=None if dq_dN is None else dq_dN[run])
+        t_rs[run], t_ss[run] = tf.T_RS_end, tf.T_SS_end
+        status[run] = tf.status
+    t_rs, t_ss, status = t_rs.reshape(N0, N1), t_ss.reshape(N0, N1), status.reshape(N0, N1)
+    return ((t_rs, t_ss), state, n_end, status) if return_status else ((t_rs, t_ss), state, n_end)

@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -334,6 +334,20 @@ class CompilationArtifact:
             "masses", _MASSES_SOURCES, "mass{key}.hsaco",
             lambda: [("INFLX_EOM_HEADER", "mass{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "mass{key}.kin.h", self.kinematics_header_text()),
                      ("INFLX_MASS_HEADER", "mass{key}.h", self.masses_header_text())],
+        )  # fmt: skip
+
+    def ensure_transfer(self) -> str:
+        """Extension: build the transfer code object of this model -- the kernels of ``inflatox_amd.background.transfer_functions``
+        (csrc/inflx_transfer_kernels.hip) -- and return its path, ``shared_object_path + ".transfer"``, where ``libinflx_hip.so``
+        looks for it.  One hipcc step on first use from the core object's header and options, the header of the equations of motion,
+        the kinematics header and the masses header, cached as ``<tag>.tr<hash>.hsaco`` (the hash covers the three generated headers
+        and ``_TRANSFER_SOURCES``, code only -- csrc/inflx_background.h among them, whose stepper pieces the kernels reuse); the
+        object carries the core object's ``MODEL_TAG`` and a layout word of its own (``INFLX_TR_ABI``).  Like the background,
+        kinematics and masses objects it lies outside the kernel groups, and none of them is involved."""
+        return self._ensure_companion(
+            "transfer", _TRANSFER_SOURCES, "tr{key}.hsaco",
+            lambda: [("INFLX_EOM_HEADER", "tr{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "tr{key}.kin.h", self.kinematics_header_text()),
+                     ("INFLX_MASS_HEADER", "tr{key}.mass.h", self.masses_header_text())],
         )  # fmt: skip
 
     def ensure_rowpass(self) -> str | None:
@@ -459,6 +473,7 @@ def _build_code_object(header_text: str, options: list[str], tag: str, groups: i
 _BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "inflx_background_abi.h", "inflx_background_rows.h")
 _KINEMATICS_SOURCES = ("inflx_kinematics_kernels.hip", "inflx_kinematics.h", "inflx_kinematics_abi.h")
 _MASSES_SOURCES = ("inflx_masses_kernels.hip", "inflx_masses.h", "inflx_masses_abi.h")
+_TRANSFER_SOURCES = ("inflx_transfer_kernels.hip", "inflx_transfer.h", "inflx_transfer_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 
