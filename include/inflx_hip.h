@@ -619,6 +619,37 @@ int inflx_transfer_functions(inflx_model* model, const double* p, size_t P, size
                              const double* samples, size_t S, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out,
                              double* ends, double* efolds, int8_t* status, uint32_t* n_stored);
 
+/*
+ * Mode functions and power spectra of n lanes, one per (trajectory, wavenumber) (csrc/inflx_modes.h): the background of
+ * inflx_solve_eom and, carried along it from the Bunch-Davies vacuum at the lane's start, the two independent complex solutions
+ * I = sigma, s of the full linear perturbation equations in the adiabatic-entropic frame (e_s = T turned counter-clockwise, the
+ * direction of inflx_transfer_functions), in the scaled variables Qt = a_in sqrt(2 k) Q, Pt = a_in sqrt(2 k) D_t Q, with
+ * Qt^I_J = delta_IJ and Pt^I_J = (-i kappa - H_in) delta_IJ at the start and k / a = kappa e^-N, N the lane's own e-fold count.
+ *   p, P, n_p, method, dt    as for inflx_solve_eom; P is 1 or n
+ *   init       (n, 4): phi^0, phi^1, chi^0, chi^1 at the lane's start; H from the Friedmann constraint
+ *   kappa      (n,): k / a at the lane's start
+ *   n_target   (n,): the e-fold count since the lane's start at which the lane is evaluated; NaN: no target
+ *   max_steps  accepted steps a lane may take
+ *   max_err    error bound of the adaptive step: the absolute Euclidean norm over phi, chi, H, the eight Qt and the eight Pt / kappa
+ *   flags      INFLX_EOM_STOP_AT_END
+ *   out        (22, n), lane fastest: P_R, P_S, C_RS = kappa^2 sum_I (|Qt^I_sigma|^2, |Qt^I_s|^2, Re Qt^I_sigma conj Qt^I_s) /
+ *              (8 pi^2 eps); the 16 mode components Qt^I_J then Pt^I_J at index 4 I + 2 J + (0: real, 1: imaginary); N; t; eps_H --
+ *              where the lane stopped with INFLX_EOM_TARGET (the state located at its target, cubic Hermite in all components) or
+ *              INFLX_EOM_ENDED (linear across the step that ends inflation at N_end's own fraction, eps_H = 1); NaN for a lane that
+ *              stopped otherwise
+ *   efolds     (n,): N at epsilon_H = 1, meaningful for INFLX_EOM_ENDED
+ *   status     (n,): inflx_eom_status; INFLX_EOM_NONFINITE at once for a lane at rest at the start (no direction), with coefficients
+ *              that are not finite there, or with a kappa that is not a positive finite number
+ * `efolds` may be NULL.  The object `<artefact>.modes` (CompilationArtifact.ensure_modes()) is loaded on first use and must carry the
+ * artefact's MODEL_TAG and this library's layout word INFLX_MD_ABI; INFLX_ERR_SYMBOL when it does not exist, INFLX_ERR_VERSION when it
+ * belongs to another model or layout.  Arguments are checked before anything touches the device.  Runs on the handle's stream in
+ * passes of at most 2^20 lanes, launches of at most 256 accepted steps, and stops launching once no lane runs any more.  A USE_GSL
+ * artefact follows the error policy of inflx_solve_eom.
+ */
+int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t n, const double* kappa,
+                       const double* n_target, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds,
+                       int8_t* status);
+
 #ifdef __cplusplus
 }
 #endif

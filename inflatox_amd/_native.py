@@ -128,6 +128,10 @@ SIGNATURES = {
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, C.POINTER(C.c_int8),
          C.POINTER(C.c_uint32)],
     ),
+    "inflx_mode_spectra": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _DP, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, C.POINTER(C.c_int8)],
+    ),
 }
 
 
@@ -142,7 +146,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -629,6 +633,32 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return out, ends, efolds, status, n_stored
+
+    # ---- mode functions and power spectra (include/inflx_hip.h: inflx_mode_spectra) ---------------
+    def mode_spectra(self, p, init, kappa, n_target, max_steps: int, method: int, max_err: float, dt: float, flags: int):
+        """n lanes from ``init`` (n,4) with the two Bunch-Davies solutions of the wavenumber ``kappa`` (n,) (k / a at the lane's
+        start) carried along, each evaluated at its own local e-fold count ``n_target`` (n,) (NaN: no target).  Returns (out (22, n):
+        P_R, P_S, C_RS, the 16 mode components, N, t, epsilon_H where the lane stopped, lane fastest; efolds; status (int8)).
+        ``flags``: ``EOM_STOP_AT_END`` or 0.  The modes object must be in place (``CompilationArtifact.ensure_modes``)."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        kappa = _f64(kappa, "kappa")
+        n_target = _f64(n_target, "n_target")
+        n = init.shape[0]
+        if kappa.shape != (n,) or n_target.shape != (n,):
+            raise InflatoxShapeError(f"kappa and n_target must have shape ({n},) (got {kappa.shape} and {n_target.shape})")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((22, n))
+        efolds = np.empty(n)
+        status = np.empty(n, dtype=np.int8)
+        _check(
+            self._lib.inflx_mode_spectra(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), n, _ptr(kappa), _ptr(n_target), int(max_steps), int(method), float(max_err), float(dt),
+                int(flags), _ptr(out), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+            )
+        )  # fmt: skip
+        return out, efolds, status
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

@@ -16,7 +16,10 @@ states -- the covariant Hesse matrix on the trajectory's own tangent and normal,
 masses built from them -- and ``mass_map`` is ``horizon_exit_map`` followed by it.  ``transfer_functions`` integrates the two
 super-horizon perturbation equations whose coefficients are that turn rate and that mass along every trajectory -- T_RS, the
 curvature perturbation sourced after horizon exit, and T_SS, the isocurvature that survives -- and ``transfer_map`` is
-``horizon_exit_map`` followed by it, from every exit state to the end of inflation.
+``horizon_exit_map`` followed by it, from every exit state to the end of inflation.  ``power_spectra`` integrates the full linear
+mode equations from the Bunch-Davies vacuum inside the horizon, one GPU lane per (trajectory, wavenumber) -- the curvature and
+isocurvature power spectra P_R and P_S and their correlation C_RS, with everything that sets the amplitude and the correlation at
+horizon exit -- and ``spectrum_map`` is ``horizon_exit_map`` followed by it.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -42,7 +45,7 @@ from .compiler import CompilationArtifact
 
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
            "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses", "transfer_functions", "transfer_map",
-           "TransferSolution"]  # fmt: skip
+           "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -696,3 +699,158 @@ def transfer_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: i
         status[run] = tf.status
     t_rs, t_ss, status = t_rs.reshape(N0, N1), t_ss.reshape(N0, N1), status.reshape(N0, N1)
     return ((t_rs, t_ss), state, n_end, status) if return_status else ((t_rs, t_ss), state, n_end)
+
+
+class PowerSpectra(NamedTuple):
+    """What :func:`power_spectra` returns, for B trajectories and K wavenumbers.  ``P_R``, ``P_S`` and ``C_RS`` (B, K): the
+    dimensionless power spectra of the curvature perturbation R = H Q_sigma / sigma_dot, of the isocurvature perturbation
+    S = H Q_s / sigma_dot and their cross-correlation at the evaluation point; ``k`` (B, K): the comoving wavenumber with a = 1 at the
+    trajectory's start, k = H_exit e^N_exit; ``N`` and ``eps_H`` (B, K): the e-fold count since the trajectory's start and epsilon_H at
+    the evaluation point (1 at the end of inflation); ``modes`` (B, K, 2, 2) complex: Qt^I_J = a_in sqrt(2 k) Q^I_J there, I the
+    Bunch-Davies solution and J the component, both in the order (sigma, s); ``N_end`` (B, K): N since the trajectory's start at
+    epsilon_H = 1 of a lane that ``ENDED``, NaN otherwise; ``status`` (B, K) int8.  The values are those of a lane that stopped
+    where it was asked to -- ``TARGET`` with ``N_eval``, ``ENDED`` without -- and NaN for every other lane, as in
+    :class:`TransferSolution`."""
+
+    P_R: np.ndarray
+    P_S: np.ndarray
+    C_RS: np.ndarray
+    k: np.ndarray
+    N: np.ndarray
+    eps_H: np.ndarray
+    modes: np.ndarray
+    N_end: np.ndarray
+    status: np.ndarray
+
+
+def _check_n_sub(N_sub):
+    try:
+        N_sub = float(N_sub)
+    except (TypeError, ValueError):
+        raise ValueError("N_sub must be a number") from None
+    if not (math.isfinite(N_sub) and N_sub > 0.0):
+        raise ValueError(f"N_sub must be finite and > 0 (got {N_sub})")
+    return N_sub
+
+
+def power_spectra(artifact: CompilationArtifact, pars, N_exit, fields_init, derivatives_init, *, N_eval=None, N_sub: float = 5.0, max_steps: int = 1_000_000,
+                  max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None, stop_at_end: bool = True) -> PowerSpectra:  # fmt: skip
+    """The curvature and isocurvature power spectra P_R, P_S and their correlation C_RS of B trajectories for K wavenumbers, from
+    the Bunch-Davies vacuum: the full linear mode equations along the trajectory (csrc/inflx_modes.h), one GPU lane per (trajectory,
+    wavenumber).  ``fields_init``, ``derivatives_init``, ``pars``, ``solver``, ``dt`` and ``max_steps`` as for ``solve_eom_sampled``.
+
+    ``N_exit`` (K,), shared by all trajectories: the e-fold counts since the start at which the modes leave the horizon, k = a H;
+    finite and >= ``N_sub``.  ``N_sub`` > 0: how many e-folds before its exit a mode starts, in the vacuum.  ``N_eval``: None -- the
+    spectra at the end of inflation, which needs ``stop_at_end`` -- or a scalar e-fold count since the start, > max(N_exit).
+
+    Stage 1 is one ``solve_eom_sampled`` run of the B trajectories at the sorted union of ``N_exit - N_sub`` and ``N_exit``: every
+    mode's start state and H at its exit, hence kappa = k / a at its start = H_exit e^N_sub.  Stage 2 runs B K lanes, numbered
+    b K + j, each from the fields and velocities of its start state (H is taken again from the Friedmann constraint, as
+    ``transfer_map`` documents).  A lane integrates the background together with two complex solutions I = sigma, s of
+
+        dQ_sigma/dt = P_sigma + Omega Q_s,      dP_sigma/dt =  Omega P_s - 3 H P_sigma - (k^2/a^2 + M_sigma_sigma) Q_sigma - M_sigma_s Q_s
+        dQ_s/dt     = P_s - Omega Q_sigma,      dP_s/dt     = -Omega P_sigma - 3 H P_s - M_sigma_s Q_sigma - (k^2/a^2 + M_ss) Q_s
+
+    in the frame (T, e_s), e_s = T turned COUNTER-CLOCKWISE in the (phi^0, phi^1) chart -- ``transfer_functions``' direction, minus
+    the normal of :class:`Kinematics` --, Omega = omega H the signed turn rate, and M_ab = V_;ab - R_acdb chi^c chi^d + (3 - eps)
+    chi_a chi_b + (chi_a V_b + V_a chi_b) / H projected on that frame; M_ss = H^2 (M_eff2 + omega^2) with :class:`Masses`' M_eff2.
+    The scaled variables Qt = a_in sqrt(2 k) Q start at Qt^I_J = delta_IJ, Pt^I_J = (-i kappa - H_in) delta_IJ, and
+
+        P_R = kappa^2 sum_I |Qt^I_sigma|^2 / (8 pi^2 eps),  P_S likewise with Qt^I_s,  C_RS = kappa^2 sum_I Re(Qt^I_sigma conj Qt^I_s) / (8 pi^2 eps)
+
+    with eps = epsilon_H at the evaluation point (1 at the end of inflation).  The steppers, acceptance rule and statuses are
+    ``solve_eom_sampled``'s; ``max_err`` bounds the absolute Euclidean norm of the error over phi, chi, H, the eight Qt and the eight
+    Pt / kappa, all O(1) at the start, so the relative error of a spectrum is about max_err e^(2 N_sub) times the number of steps
+    over its own size.  With ``N_eval`` the evaluation point is located as ``state_at_efolds`` locates it, all components with the same
+    cubic Hermite interpolant; at the end of inflation the modes are linear across the step that ends it, at N_end's own fraction.
+    A lane whose stage 1 samples were not reached keeps stage 1's status and NaN values; a lane at rest at its start is
+    ``NONFINITE``.  The kernels are built into ``<artefact>.modes`` on first use (``CompilationArtifact.ensure_modes``).  Bad
+    arguments raise before anything runs on the device."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    try:
+        n_exit = np.ascontiguousarray(N_exit, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("N_exit must be convertible to a float64 array") from None
+    if n_exit.ndim != 1:
+        raise InflatoxShapeError(f"N_exit must be one-dimensional (got shape {n_exit.shape})")
+    if n_exit.size < 1:
+        raise ValueError("N_exit must hold at least one e-fold count")
+    N_sub = _check_n_sub(N_sub)
+    if not (np.isfinite(n_exit).all() and (n_exit >= N_sub).all()):
+        raise ValueError(f"N_exit must be finite and >= N_sub = {N_sub}")
+    if N_eval is None:
+        if not stop_at_end:
+            raise ValueError("N_eval=None evaluates at the end of inflation and needs stop_at_end")
+    else:
+        try:
+            N_eval = float(N_eval)
+        except (TypeError, ValueError):
+            raise ValueError("N_eval must be None or a number") from None
+        if not (math.isfinite(N_eval) and N_eval > n_exit.max()):
+            raise ValueError(f"N_eval must be finite and > max(N_exit) = {n_exit.max()} (got {N_eval})")
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    B, K = x.shape[0], n_exit.size
+    p = _pars(artifact, pars, B)
+    starts = n_exit - N_sub
+    pts, inverse = np.unique(np.concatenate([starts, n_exit]), return_inverse=True)
+    bg = solve_eom_sampled(artifact, p, pts, x, v, max_steps, max_err, solver, dt=dt, stop_at_end=stop_at_end)
+    start = bg.states[:, inverse[:K], :4]  # (B, K, 4)
+    h_exit = bg.states[:, inverse[K:], 4]  # (B, K)
+    kappa = h_exit * math.exp(N_sub)
+    status = np.repeat(bg.status[:, None], K, axis=1).reshape(-1)
+    out = np.full((22, B * K), np.nan)
+    n_end = np.full(B * K, np.nan)
+    run = np.flatnonzero((np.isfinite(start).all(axis=2) & np.isfinite(h_exit)).reshape(-1))
+    lane_start = np.tile(starts, B)
+    if run.size:
+        target = np.full(run.size, np.nan) if N_eval is None else N_eval - lane_start[run]
+        artifact.ensure_modes()
+        lib = _dylib(artifact, background=False)
+        lane_p = p if p.ndim == 1 else np.ascontiguousarray(np.repeat(p, K, axis=0)[run])
+        flags = _native.EOM_STOP_AT_END if stop_at_end else 0
+        got, ends, st = lib.mode_spectra(lane_p, np.ascontiguousarray(start.reshape(-1, 4)[run]), np.ascontiguousarray(kappa.reshape(-1)[run]), target, max_steps,
+                                         _METHODS[solver], max_err, dt or 0.0, flags)  # fmt: skip
+        valid = st == (ENDED if N_eval is None else TARGET)
+        out[:, run] = np.where(valid[None, :], got, np.nan)
+        n_end[run] = np.where(st == ENDED, ends, np.nan)
+        status[run] = st
+    out = out.reshape(22, B, K)
+    offset = lane_start.reshape(B, K)
+    q = out[3:11].reshape(2, 2, 2, B, K)  # [I][J][re, im]
+    modes = np.moveaxis(q[:, :, 0] + 1j * q[:, :, 1], (0, 1), (2, 3))
+    return PowerSpectra(out[0], out[1], out[2], h_exit * np.exp(n_exit)[None, :], out[19] + offset, out[21], modes, n_end.reshape(B, K) + offset,
+                        status.reshape(B, K))  # fmt: skip
+
+
+def spectrum_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, N_sub: float = 5.0, derivatives_init=(0.0, 0.0),
+                 max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """``horizon_exit_map`` with ``N_star + N_sub`` (otherwise the same arguments) followed by ``power_spectra(N_exit=[N_sub])`` from
+    every state found to the end of inflation: ``((P_R, P_S, C_RS), state, N_end)`` with the three (N0, N1) spectra at the end of
+    inflation of the mode that leaves the horizon ``N_star`` e-folds before it, from the trajectory of every grid point, and ``state``
+    (N0, N1, 5) and ``N_end`` (N0, N1) exactly ``horizon_exit_map``'s at ``N_star + N_sub``: the state at which the mode starts, in
+    the vacuum, ``N_sub`` e-folds before its exit.  As in ``transfer_map`` the second stage takes H again from the Friedmann
+    constraint.  NaN where no such state was found or the second stage did not reach the end of inflation;
+    ``return_status=True`` adds the (N0, N1) status map: ``horizon_exit_map``'s, with the second stage's status (``ENDED`` where the
+    spectra are valid) in place of ``TARGET``."""
+    N_sub = _check_n_sub(N_sub)
+    try:
+        N_star = float(N_star)
+    except (TypeError, ValueError):
+        raise ValueError("N_star must be a number") from None
+    if not (math.isfinite(N_star) and N_star >= 0.0):
+        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star + N_sub, derivatives_init, max_steps, max_err, solver, return_status=True)
+    N0, N1 = n_end.shape
+    flat = state.reshape(-1, 5)
+    status = status.copy().reshape(-1)
+    spectra = np.full((3, N0 * N1), np.nan)
+    run = np.flatnonzero(status == TARGET)
+    if run.size:
+        ps = power_spectra(artifact, pars, [N_sub], flat[run, :2], flat[run, 2:4], N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver)
+        spectra[:, run] = ps.P_R[:, 0], ps.P_S[:, 0], ps.C_RS[:, 0]
+        status[run] = ps.status[:, 0]
+    spectra, status = spectra.reshape(3, N0, N1), status.reshape(N0, N1)
+    return (tuple(spectra), state, n_end, status) if return_status else (tuple(spectra), state, n_end)

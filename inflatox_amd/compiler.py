@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -350,6 +350,20 @@ class CompilationArtifact:
                      ("INFLX_MASS_HEADER", "tr{key}.mass.h", self.masses_header_text())],
         )  # fmt: skip
 
+    def ensure_modes(self) -> str:
+        """Extension: build the modes code object of this model -- the kernels of ``inflatox_amd.background.power_spectra``
+        (csrc/inflx_modes_kernels.hip) -- and return its path, ``shared_object_path + ".modes"``, where ``libinflx_hip.so`` looks
+        for it.  One hipcc step on first use from the core object's header and options, the header of the equations of motion, the
+        kinematics header and the masses header, cached as ``<tag>.md<hash>.hsaco`` (the hash covers the three generated headers and
+        ``_MODES_SOURCES``, code only -- csrc/inflx_background.h among them, whose stepper pieces the kernels reuse); the object
+        carries the core object's ``MODEL_TAG`` and a layout word of its own (``INFLX_MD_ABI``).  Like the background, kinematics,
+        masses and transfer objects it lies outside the kernel groups, and none of them is involved."""
+        return self._ensure_companion(
+            "modes", _MODES_SOURCES, "md{key}.hsaco",
+            lambda: [("INFLX_EOM_HEADER", "md{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "md{key}.kin.h", self.kinematics_header_text()),
+                     ("INFLX_MASS_HEADER", "md{key}.mass.h", self.masses_header_text())],
+        )  # fmt: skip
+
     def ensure_rowpass(self) -> str | None:
         """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
         evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
@@ -474,6 +488,7 @@ _BACKGROUND_SOURCES = ("inflx_background_kernels.hip", "inflx_background.h", "in
 _KINEMATICS_SOURCES = ("inflx_kinematics_kernels.hip", "inflx_kinematics.h", "inflx_kinematics_abi.h")
 _MASSES_SOURCES = ("inflx_masses_kernels.hip", "inflx_masses.h", "inflx_masses_abi.h")
 _TRANSFER_SOURCES = ("inflx_transfer_kernels.hip", "inflx_transfer.h", "inflx_transfer_abi.h", "inflx_background.h", "inflx_background_abi.h")
+_MODES_SOURCES = ("inflx_modes_kernels.hip", "inflx_modes.h", "inflx_modes_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 
