@@ -445,6 +445,9 @@ typedef enum inflx_eom_flags {
   INFLX_EOM_SAMPLE_T = 4,   /* inflx_solve_eom_sampled: the samples are times, not e-fold counts */
   INFLX_EOM_HOST_SCATTER = 8 /* inflx_solve_eom: rearrange the rows on the host, not with the transpose kernel */
 } inflx_eom_flags;
+typedef enum inflx_modes_flags {
+  INFLX_MODES_TENSOR = 8 /* inflx_mode_spectra: the lanes carry one tensor mode instead of the scalar perturbations, `out` is (8, n) */
+} inflx_modes_flags;
 typedef enum inflx_eom_status {
   INFLX_EOM_COMPLETE = 0,   /* every requested step was taken */
   INFLX_EOM_ENDED = 1,      /* epsilon_H reached 1 (INFLX_EOM_STOP_AT_END) */
@@ -631,7 +634,7 @@ int inflx_transfer_functions(inflx_model* model, const double* p, size_t P, size
  *   n_target   (n,): the e-fold count since the lane's start at which the lane is evaluated; NaN: no target
  *   max_steps  accepted steps a lane may take
  *   max_err    error bound of the adaptive step: the absolute Euclidean norm over phi, chi, H, the eight Qt and the eight Pt / kappa
- *   flags      INFLX_EOM_STOP_AT_END
+ *   flags      INFLX_EOM_STOP_AT_END, INFLX_MODES_TENSOR (below)
  *   out        (22, n), lane fastest: P_R, P_S, C_RS = kappa^2 sum_I (|Qt^I_sigma|^2, |Qt^I_s|^2, Re Qt^I_sigma conj Qt^I_s) /
  *              (8 pi^2 eps); the 16 mode components Qt^I_J then Pt^I_J at index 4 I + 2 J + (0: real, 1: imaginary); N; t; eps_H --
  *              where the lane stopped with INFLX_EOM_TARGET (the state located at its target, cubic Hermite in all components) or
@@ -645,6 +648,19 @@ int inflx_transfer_functions(inflx_model* model, const double* p, size_t P, size
  * belongs to another model or layout.  Arguments are checked before anything touches the device.  Runs on the handle's stream in
  * passes of at most 2^20 lanes, launches of at most 256 accepted steps, and stops launching once no lane runs any more.  A USE_GSL
  * artefact follows the error policy of inflx_solve_eom.
+ *
+ * With INFLX_MODES_TENSOR in `flags` the lanes carry one tensor mode instead (csrc/inflx_tensor.h): the same arguments, checks, passes
+ * and statuses, and along the same background one complex amplitude ht = a_in sqrt(2 k) u, pt = d ht/dt, with u = h / 2 the
+ * canonically normalised amplitude of one polarisation in reduced Planck units:
+ *     d ht/dt = pt,   d pt/dt = -3 H pt - kappa^2 e^-2N ht,   ht = 1 and pt = -i kappa - H_in at the start.
+ *   max_err    the absolute Euclidean norm over phi, chi, H, the two components of ht and the two of pt / kappa
+ *   out        (8, n), lane fastest: P_T = 2 kappa^2 |ht|^2 / pi^2 (both polarisations: 2 H^2 / pi^2 in de Sitter, and P_T / P_R = 16 eps
+ *              in single-field slow roll); Re ht, Im ht, Re pt, Im pt; N; t; eps_H -- located and interpolated as above
+ *   status     a lane at rest at the start is NOT an error here (a tensor mode needs no direction in field space): it runs like any
+ *              other; INFLX_EOM_NONFINITE for a state or right-hand side that is not finite or a kappa that is not a positive
+ *              finite number
+ * The object is `<artefact>.tensor` (CompilationArtifact.ensure_tensor()) with the layout word INFLX_TN_ABI, loaded on first use and
+ * refused in the same two ways; the modes object is not needed.  A call without the flag is not affected by one with it.
  */
 int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p, const double* init, size_t n, const double* kappa,
                        const double* n_target, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds,

@@ -33,6 +33,7 @@ SWEEP_DEFAULT, SWEEP_FORCE_TILE = 0, 1  # inflx_sweep_flags
 TIME_BACK_TO_BACK, TIME_DOMINANT_ONLY, TIME_IN_PIPELINE, TIME_SINGLE_CALL = range(4)  # inflx_timing
 EOM_RK4, EOM_RKF = 0, 1  # inflx_eom_method
 EOM_STOP_AT_END, EOM_FINAL_ONLY, EOM_SAMPLE_T, EOM_HOST_SCATTER = 1, 2, 4, 8  # inflx_eom_flags
+MODES_TENSOR = 8  # inflx_modes_flags (inflx_mode_spectra only): tensor-mode lanes, out (8, n)
 GATHER_PEER_PUSH, GATHER_RCCL = 0, 1  # inflx_gather: the exchange step of inflx_sweep_allgather_multi_ex
 
 _DP = C.POINTER(C.c_double)
@@ -146,7 +147,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -639,7 +640,9 @@ class InflatoxDevLib:
         """n lanes from ``init`` (n,4) with the two Bunch-Davies solutions of the wavenumber ``kappa`` (n,) (k / a at the lane's
         start) carried along, each evaluated at its own local e-fold count ``n_target`` (n,) (NaN: no target).  Returns (out (22, n):
         P_R, P_S, C_RS, the 16 mode components, N, t, epsilon_H where the lane stopped, lane fastest; efolds; status (int8)).
-        ``flags``: ``EOM_STOP_AT_END`` or 0.  The modes object must be in place (``CompilationArtifact.ensure_modes``)."""
+        ``flags``: ``EOM_STOP_AT_END`` or 0.  The modes object must be in place (``CompilationArtifact.ensure_modes``).
+        With ``MODES_TENSOR`` in ``flags`` the lanes carry one tensor mode instead (csrc/inflx_tensor.h): out is (8, n) -- P_T, Re ht,
+        Im ht, Re pt, Im pt, N, t, epsilon_H -- and the tensor object must be in place (``CompilationArtifact.ensure_tensor``)."""
         init = _f64(init, "init")
         p = _f64(p, "p")
         kappa = _f64(kappa, "kappa")
@@ -649,7 +652,7 @@ class InflatoxDevLib:
             raise InflatoxShapeError(f"kappa and n_target must have shape ({n},) (got {kappa.shape} and {n_target.shape})")
         P = 1 if p.ndim <= 1 else p.shape[0]
         p = p.reshape(-1)
-        out = np.empty((22, n))
+        out = np.empty((8 if int(flags) & MODES_TENSOR else 22, n))
         efolds = np.empty(n)
         status = np.empty(n, dtype=np.int8)
         _check(

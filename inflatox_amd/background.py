@@ -19,7 +19,10 @@ curvature perturbation sourced after horizon exit, and T_SS, the isocurvature th
 ``horizon_exit_map`` followed by it, from every exit state to the end of inflation.  ``power_spectra`` integrates the full linear
 mode equations from the Bunch-Davies vacuum inside the horizon, one GPU lane per (trajectory, wavenumber) -- the curvature and
 isocurvature power spectra P_R and P_S and their correlation C_RS, with everything that sets the amplitude and the correlation at
-horizon exit -- and ``spectrum_map`` is ``horizon_exit_map`` followed by it.
+horizon exit -- and ``spectrum_map`` is ``horizon_exit_map`` followed by it.  ``tensor_spectra`` is its tensor twin, the tensor power
+spectrum P_T from one complex tensor amplitude per lane; ``observables`` differences both in ln k around a pivot of the trajectory's
+own -- the scalar tilt n_s, its running, the tensor tilt n_t and the tensor-to-scalar ratio r -- and ``observables_map`` is
+``horizon_exit_map`` followed by it: n_s and r, as maps, of the mode that leaves the horizon N_star e-folds before the end of inflation.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -45,7 +48,7 @@ from .compiler import CompilationArtifact
 
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
            "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses", "transfer_functions", "transfer_map",
-           "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra"]  # fmt: skip
+           "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra", "tensor_spectra", "TensorSpectra", "observables", "Observables", "observables_map"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -733,6 +736,74 @@ def _check_n_sub(N_sub):
     return N_sub
 
 
+def _check_spectra(artifact, pars, N_exit, fields_init, derivatives_init, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end):
+    """The argument checks of ``power_spectra`` and ``tensor_spectra``, in their order: (p, n_exit (K,), x, v (B, 2), N_eval, N_sub,
+    max_steps, max_err, solver, dt, stop_at_end), what ``_mode_lanes`` takes."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    try:
+        n_exit = np.ascontiguousarray(N_exit, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("N_exit must be convertible to a float64 array") from None
+    if n_exit.ndim != 1:
+        raise InflatoxShapeError(f"N_exit must be one-dimensional (got shape {n_exit.shape})")
+    if n_exit.size < 1:
+        raise ValueError("N_exit must hold at least one e-fold count")
+    N_sub = _check_n_sub(N_sub)
+    if not (np.isfinite(n_exit).all() and (n_exit >= N_sub).all()):
+        raise ValueError(f"N_exit must be finite and >= N_sub = {N_sub}")
+    if N_eval is None:
+        if not stop_at_end:
+            raise ValueError("N_eval=None evaluates at the end of inflation and needs stop_at_end")
+    else:
+        try:
+            N_eval = float(N_eval)
+        except (TypeError, ValueError):
+            raise ValueError("N_eval must be None or a number") from None
+        if not (math.isfinite(N_eval) and N_eval > n_exit.max()):
+            raise ValueError(f"N_eval must be finite and > max(N_exit) = {n_exit.max()} (got {N_eval})")
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    B, K = x.shape[0], n_exit.size
+    p = _pars(artifact, pars, B)
+    return p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end
+
+
+def _mode_lanes(artifact, tensor, p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end):
+    """The two stages of ``power_spectra`` (``tensor``: of ``tensor_spectra``, whose first stage is the same call) on checked
+    arguments: (out (planes, B K) with NaN for a lane that did not stop where asked, h_exit (B, K), n_exit, lane_start (B K,),
+    n_end (B K,), status (B K,))."""
+    B, K = x.shape[0], n_exit.size
+    starts = n_exit - N_sub
+    pts, inverse = np.unique(np.concatenate([starts, n_exit]), return_inverse=True)
+    bg = solve_eom_sampled(artifact, p, pts, x, v, max_steps, max_err, solver, dt=dt, stop_at_end=stop_at_end)
+    start = bg.states[:, inverse[:K], :4]  # (B, K, 4)
+    h_exit = bg.states[:, inverse[K:], 4]  # (B, K)
+    kappa = h_exit * math.exp(N_sub)
+    status = np.repeat(bg.status[:, None], K, axis=1).reshape(-1)
+    out = np.full((8 if tensor else 22, B * K), np.nan)
+    n_end = np.full(B * K, np.nan)
+    run = np.flatnonzero((np.isfinite(start).all(axis=2) & np.isfinite(h_exit)).reshape(-1))
+    lane_start = np.tile(starts, B)
+    if run.size:
+        target = np.full(run.size, np.nan) if N_eval is None else N_eval - lane_start[run]
+        if tensor:
+            artifact.ensure_tensor()
+        else:
+            artifact.ensure_modes()
+        lib = _dylib(artifact, background=False)
+        lane_p = p if p.ndim == 1 else np.ascontiguousarray(np.repeat(p, K, axis=0)[run])
+        flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.MODES_TENSOR if tensor else 0)
+        got, ends, st = lib.mode_spectra(lane_p, np.ascontiguousarray(start.reshape(-1, 4)[run]), np.ascontiguousarray(kappa.reshape(-1)[run]), target, max_steps,
+                                         _METHODS[solver], max_err, dt or 0.0, flags)  # fmt: skip
+        valid = st == (ENDED if N_eval is None else TARGET)
+        out[:, run] = np.where(valid[None, :], got, np.nan)
+        n_end[run] = np.where(st == ENDED, ends, np.nan)
+        status[run] = st
+    return out, h_exit, n_exit, lane_start, n_end, status
+
+
 def power_spectra(artifact: CompilationArtifact, pars, N_exit, fields_init, derivatives_init, *, N_eval=None, N_sub: float = 5.0, max_steps: int = 1_000_000,
                   max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None, stop_at_end: bool = True) -> PowerSpectra:  # fmt: skip
     """The curvature and isocurvature power spectra P_R, P_S and their correlation C_RS of B trajectories for K wavenumbers, from
@@ -766,57 +837,9 @@ def power_spectra(artifact: CompilationArtifact, pars, N_exit, fields_init, deri
     A lane whose stage 1 samples were not reached keeps stage 1's status and NaN values; a lane at rest at its start is
     ``NONFINITE``.  The kernels are built into ``<artefact>.modes`` on first use (``CompilationArtifact.ensure_modes``).  Bad
     arguments raise before anything runs on the device."""
-    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
-    try:
-        n_exit = np.ascontiguousarray(N_exit, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("N_exit must be convertible to a float64 array") from None
-    if n_exit.ndim != 1:
-        raise InflatoxShapeError(f"N_exit must be one-dimensional (got shape {n_exit.shape})")
-    if n_exit.size < 1:
-        raise ValueError("N_exit must hold at least one e-fold count")
-    N_sub = _check_n_sub(N_sub)
-    if not (np.isfinite(n_exit).all() and (n_exit >= N_sub).all()):
-        raise ValueError(f"N_exit must be finite and >= N_sub = {N_sub}")
-    if N_eval is None:
-        if not stop_at_end:
-            raise ValueError("N_eval=None evaluates at the end of inflation and needs stop_at_end")
-    else:
-        try:
-            N_eval = float(N_eval)
-        except (TypeError, ValueError):
-            raise ValueError("N_eval must be None or a number") from None
-        if not (math.isfinite(N_eval) and N_eval > n_exit.max()):
-            raise ValueError(f"N_eval must be finite and > max(N_exit) = {n_exit.max()} (got {N_eval})")
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
-    B, K = x.shape[0], n_exit.size
-    p = _pars(artifact, pars, B)
-    starts = n_exit - N_sub
-    pts, inverse = np.unique(np.concatenate([starts, n_exit]), return_inverse=True)
-    bg = solve_eom_sampled(artifact, p, pts, x, v, max_steps, max_err, solver, dt=dt, stop_at_end=stop_at_end)
-    start = bg.states[:, inverse[:K], :4]  # (B, K, 4)
-    h_exit = bg.states[:, inverse[K:], 4]  # (B, K)
-    kappa = h_exit * math.exp(N_sub)
-    status = np.repeat(bg.status[:, None], K, axis=1).reshape(-1)
-    out = np.full((22, B * K), np.nan)
-    n_end = np.full(B * K, np.nan)
-    run = np.flatnonzero((np.isfinite(start).all(axis=2) & np.isfinite(h_exit)).reshape(-1))
-    lane_start = np.tile(starts, B)
-    if run.size:
-        target = np.full(run.size, np.nan) if N_eval is None else N_eval - lane_start[run]
-        artifact.ensure_modes()
-        lib = _dylib(artifact, background=False)
-        lane_p = p if p.ndim == 1 else np.ascontiguousarray(np.repeat(p, K, axis=0)[run])
-        flags = _native.EOM_STOP_AT_END if stop_at_end else 0
-        got, ends, st = lib.mode_spectra(lane_p, np.ascontiguousarray(start.reshape(-1, 4)[run]), np.ascontiguousarray(kappa.reshape(-1)[run]), target, max_steps,
-                                         _METHODS[solver], max_err, dt or 0.0, flags)  # fmt: skip
-        valid = st == (ENDED if N_eval is None else TARGET)
-        out[:, run] = np.where(valid[None, :], got, np.nan)
-        n_end[run] = np.where(st == ENDED, ends, np.nan)
-        status[run] = st
+    args = _check_spectra(artifact, pars, N_exit, fields_init, derivatives_init, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
+    out, h_exit, n_exit, lane_start, n_end, status = _mode_lanes(artifact, False, *args)
+    B, K = h_exit.shape
     out = out.reshape(22, B, K)
     offset = lane_start.reshape(B, K)
     q = out[3:11].reshape(2, 2, 2, B, K)  # [I][J][re, im]
@@ -854,3 +877,189 @@ def spectrum_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: i
         status[run] = ps.status[:, 0]
     spectra, status = spectra.reshape(3, N0, N1), status.reshape(N0, N1)
     return (tuple(spectra), state, n_end, status) if return_status else (tuple(spectra), state, n_end)
+
+
+class TensorSpectra(NamedTuple):
+    """What :func:`tensor_spectra` returns, for B trajectories and K wavenumbers.  ``P_T`` (B, K): the dimensionless tensor power
+    spectrum, both polarisations, at the evaluation point; ``k``, ``N`` and ``eps_H`` (B, K) as in :class:`PowerSpectra` (``k`` is
+    ``power_spectra``'s bit for bit); ``modes`` (B, K) complex: ht = a_in sqrt(2 k) u there, u = h / 2 the canonically normalised
+    amplitude of one polarisation; ``N_end`` and ``status`` (B, K) as in :class:`PowerSpectra`.  The values are those of a lane that
+    stopped where it was asked to and NaN for every other lane."""
+
+    P_T: np.ndarray
+    k: np.ndarray
+    N: np.ndarray
+    eps_H: np.ndarray
+    modes: np.ndarray
+    N_end: np.ndarray
+    status: np.ndarray
+
+
+def tensor_spectra(artifact: CompilationArtifact, pars, N_exit, fields_init, derivatives_init, *, N_eval=None, N_sub: float = 5.0, max_steps: int = 1_000_000,
+                   max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None, stop_at_end: bool = True) -> TensorSpectra:  # fmt: skip
+    """The tensor power spectrum P_T of B trajectories for K wavenumbers, from the Bunch-Davies vacuum: ``power_spectra``'s tensor
+    twin (csrc/inflx_tensor.h), one GPU lane per (trajectory, wavenumber).  The arguments, their checks and their order, the two stages
+    and the lane numbering b K + j are ``power_spectra``'s; stage 1 is the identical ``solve_eom_sampled`` call, so ``k`` is
+    ``power_spectra``'s bit for bit.  A lane integrates the background together with one complex amplitude
+
+        d ht/dt = pt,      d pt/dt = -3 H pt - (k^2/a^2) ht,      ht = a_in sqrt(2 k) u,   u = h / 2
+
+    in reduced Planck units (those of dH/dt = V - 3 H^2), from ht = 1, pt = -i kappa - H_in, and
+
+        P_T = 2 kappa^2 |ht|^2 / pi^2
+
+    counts both polarisations: 2 H^2 / pi^2 in de Sitter, and r = P_T / P_R = 16 eps in single-field slow roll with ``power_spectra``'s
+    P_R.  ``max_err`` bounds the absolute Euclidean norm of the error over phi, chi, H, the two components of ht and the two of
+    pt / kappa.  The evaluation point is located and interpolated as in ``power_spectra``.  A lane at rest at its start is NOT an
+    error here: a tensor mode needs no direction in field space and P_T does not divide by epsilon_H.  The kernels are built into
+    ``<artefact>.tensor`` on first use (``CompilationArtifact.ensure_tensor``).  Bad arguments raise before anything runs on the
+    device."""
+    args = _check_spectra(artifact, pars, N_exit, fields_init, derivatives_init, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
+    out, h_exit, n_exit, lane_start, n_end, status = _mode_lanes(artifact, True, *args)
+    B, K = h_exit.shape
+    out = out.reshape(8, B, K)
+    offset = lane_start.reshape(B, K)
+    return TensorSpectra(out[0], h_exit * np.exp(n_exit)[None, :], out[5] + offset, out[7], out[1] + 1j * out[2], n_end.reshape(B, K) + offset,
+                         status.reshape(B, K))  # fmt: skip
+
+
+class Observables(NamedTuple):
+    """What :func:`observables` returns, for B trajectories and K pivots, all (B, K).  ``A_s`` = P_R and ``A_t`` = P_T at the pivot
+    wavenumber; ``r`` = P_T / P_R; ``n_s`` = 1 + d ln P_R / d ln k; ``alpha_s`` = d^2 ln P_R / d ln k^2; ``n_t`` = d ln P_T / d ln k;
+    ``beta_iso`` = P_S / (P_R + P_S); ``cos_delta`` = C_RS / sqrt(P_R P_S); ``k``: the pivot's comoving wavenumber; ``N_end``: that of
+    the pivot's scalar lane; ``status`` int8: the status asked for (``ENDED``, or ``TARGET`` with ``N_eval``) when all six lanes of a
+    pivot -- scalar and tensor, at the pivot and ``dN`` on either side -- stopped there, otherwise the largest status code among the
+    lanes that did not.  Every value but ``k``, ``N_end`` and ``status`` is NaN unless all six did."""
+
+    A_s: np.ndarray
+    A_t: np.ndarray
+    r: np.ndarray
+    n_s: np.ndarray
+    alpha_s: np.ndarray
+    n_t: np.ndarray
+    beta_iso: np.ndarray
+    cos_delta: np.ndarray
+    k: np.ndarray
+    N_end: np.ndarray
+    status: np.ndarray
+
+
+def log_slopes(k, P):
+    """First and second derivative of ln P in ln k at the middle of three points: ``k`` and ``P`` (..., 3), ordered (below, pivot,
+    above).  With x = ln k, f = ln P, h1 = x_0 - x_m and h2 = x_p - x_0 -- not equal, because H changes along a trajectory -- the
+    Lagrange quadratic through the three points has, at x_0,
+
+        f'  = -h2 / (h1 (h1 + h2)) f_m + (h2 - h1) / (h1 h2) f_0 + h1 / (h2 (h1 + h2)) f_p
+        f'' = 2 [f_m / (h1 (h1 + h2)) - f_0 / (h1 h2) + f_p / (h2 (h1 + h2))]
+
+    A pure function of its two arrays.  Returns (f', f'')."""
+    w1, w2 = stencil_weights(k)
+    f = np.log(np.asarray(P, dtype=np.float64))
+    return (w1 * f).sum(axis=-1), (w2 * f).sum(axis=-1)
+
+
+def stencil_weights(k):
+    """The weights (..., 3) of ``log_slopes``' two formulas on (f_m, f_0, f_p), from ``k`` (..., 3): (first, second)."""
+    x = np.log(np.asarray(k, dtype=np.float64))
+    h1, h2 = x[..., 1] - x[..., 0], x[..., 2] - x[..., 1]
+    s = h1 + h2
+    first = np.stack([-h2 / (h1 * s), (h2 - h1) / (h1 * h2), h1 / (h2 * s)], axis=-1)
+    second = 2.0 * np.stack([1.0 / (h1 * s), -1.0 / (h1 * h2), 1.0 / (h2 * s)], axis=-1)
+    return first, second
+
+
+def observables_from_spectra(scalar, tensor, columns, wanted) -> Observables:
+    """The differencing half of :func:`observables`, a pure function: ``scalar`` and ``tensor`` with the members of
+    :class:`PowerSpectra` and :class:`TensorSpectra` over (B, U) wavenumbers, ``columns`` (3, K) the columns of (below, pivot, above)
+    of every pivot, ``wanted`` the status of a lane that stopped where asked."""
+    cols = np.asarray(columns)
+    k3 = np.moveaxis(scalar.k[:, cols], 1, -1)  # (B, K, 3)
+    pr3, pt3 = np.moveaxis(scalar.P_R[:, cols], 1, -1), np.moveaxis(tensor.P_T[:, cols], 1, -1)
+    st6 = np.concatenate([np.moveaxis(scalar.status[:, cols], 1, -1), np.moveaxis(tensor.status[:, cols], 1, -1)], axis=-1)  # (B, K, 6)
+    ok = (st6 == wanted).all(axis=-1)
+    status = np.where(ok, wanted, np.where(st6 == wanted, -1, st6).max(axis=-1)).astype(np.int8)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d1s, d2s = log_slopes(k3, pr3)
+        d1t, _ = log_slopes(k3, pt3)
+        mid = cols[1]
+        p_r, p_s, c_rs, p_t = scalar.P_R[:, mid], scalar.P_S[:, mid], scalar.C_RS[:, mid], tensor.P_T[:, mid]
+        values = [p_r, p_t, p_t / p_r, 1.0 + d1s, d2s, d1t, p_s / (p_r + p_s), c_rs / np.sqrt(p_r * p_s)]
+    values = [np.where(ok, v, np.nan) for v in values]
+    return Observables(*values, scalar.k[:, mid], scalar.N_end[:, mid], status)
+
+
+def _check_dn(dN):
+    try:
+        dN = float(dN)
+    except (TypeError, ValueError):
+        raise ValueError("dN must be a number") from None
+    if not (math.isfinite(dN) and dN > 0.0):
+        raise ValueError(f"dN must be finite and > 0 (got {dN})")
+    return dN
+
+
+def observables(artifact: CompilationArtifact, pars, N_exit, fields_init, derivatives_init, *, dN: float = 0.5, N_eval=None, N_sub: float = 5.0,
+                max_steps: int = 1_000_000, max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None, stop_at_end: bool = True) -> Observables:  # fmt: skip
+    """The scalar amplitude and tilt, the running, the tensor amplitude and tilt, the tensor-to-scalar ratio and the isocurvature
+    fraction of B trajectories at K pivots ``N_exit`` (the e-fold counts since the start at which the pivot modes leave the horizon):
+    one ``power_spectra`` call and one ``tensor_spectra`` call on the sorted, de-duplicated union of ``N_exit - dN``, ``N_exit`` and
+    ``N_exit + dN``, differenced per trajectory in ln k around its own pivot.  The other arguments are ``power_spectra``'s.
+
+    ``dN`` must be finite and > 0, ``N_exit - dN >= N_sub`` (a lower point within a rounding of ``N_sub`` counts as ``N_sub``) and
+    ``N_eval > max(N_exit) + dN``; everything raises before the device is touched.
+
+    Per trajectory x = ln k at the three wavenumbers is its own -- k = H_exit e^N_exit, not equally spaced because H changes -- and
+    with f = ln P, h1 = x_0 - x_m, h2 = x_p - x_0 the derivatives are those of the Lagrange quadratic through the three points at x_0:
+
+        f'  = -h2 / (h1 (h1 + h2)) f_m + (h2 - h1) / (h1 h2) f_0 + h1 / (h2 (h1 + h2)) f_p
+        f'' = 2 [f_m / (h1 (h1 + h2)) - f_0 / (h1 h2) + f_p / (h2 (h1 + h2))]
+
+    (``log_slopes``); n_s = 1 + f'[P_R], alpha_s = f''[P_R], n_t = f'[P_T].  The quadratic's own error is of order dN^2 times the third
+    derivative of ln P.  See :class:`Observables` for the members and for ``status``."""
+    dN = _check_dn(dN)
+    p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end = _check_spectra(
+        artifact, pars, N_exit, fields_init, derivatives_init, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)  # fmt: skip
+    below = n_exit - dN
+    below = np.where(np.abs(below - N_sub) <= 4.0 * np.finfo(np.float64).eps * max(1.0, N_sub), N_sub, below)
+    if not (below >= N_sub).all():
+        raise ValueError(f"N_exit - dN must be >= N_sub = {N_sub}")
+    if N_eval is not None and not N_eval > n_exit.max() + dN:
+        raise ValueError(f"N_eval must be > max(N_exit) + dN = {n_exit.max() + dN} (got {N_eval})")
+    pts, inverse = np.unique(np.concatenate([below, n_exit, n_exit + dN]), return_inverse=True)
+    kw = dict(N_eval=N_eval, N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver, dt=dt, stop_at_end=stop_at_end)
+    scalar = power_spectra(artifact, p, pts, x, v, **kw)
+    tensor = tensor_spectra(artifact, p, pts, x, v, **kw)
+    return observables_from_spectra(scalar, tensor, inverse.reshape(3, n_exit.size), ENDED if N_eval is None else TARGET)
+
+
+def observables_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, dN: float = 0.5, N_sub: float = 5.0,
+                    derivatives_init=(0.0, 0.0), max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """``horizon_exit_map`` with ``N_star + N_sub + dN`` (otherwise the same arguments) followed by ``observables(N_exit=[N_sub + dN])``
+    from every state found to the end of inflation: ``(obs, state, N_end)`` with ``obs`` the :class:`Observables` of (N0, N1) arrays
+    -- n_s, r and the others of the mode that leaves the horizon ``N_star`` e-folds before the end of inflation, from the trajectory of
+    every grid point -- and ``state`` (N0, N1, 5) and ``N_end`` (N0, N1) exactly ``horizon_exit_map``'s at ``N_star + N_sub + dN``: the
+    state at which the lowest of the three modes starts, in the vacuum.  As in ``spectrum_map`` the second stage takes H again from
+    the Friedmann constraint.  NaN where no such state was found or one of the six lanes did not reach the end of inflation;
+    ``obs.status`` and, with ``return_status=True``, a fourth member are the (N0, N1) status map: ``horizon_exit_map``'s, with
+    ``observables``' status (``ENDED`` where the values are valid) in place of ``TARGET``."""
+    N_sub = _check_n_sub(N_sub)
+    dN = _check_dn(dN)
+    try:
+        N_star = float(N_star)
+    except (TypeError, ValueError):
+        raise ValueError("N_star must be a number") from None
+    if not (math.isfinite(N_star) and N_star >= 0.0):
+        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star + N_sub + dN, derivatives_init, max_steps, max_err, solver, return_status=True)
+    N0, N1 = n_end.shape
+    flat = state.reshape(-1, 5)
+    status = status.copy().reshape(-1)
+    values = np.full((len(Observables._fields) - 1, N0 * N1), np.nan)
+    run = np.flatnonzero(status == TARGET)
+    if run.size:
+        obs = observables(artifact, pars, [N_sub + dN], flat[run, :2], flat[run, 2:4], dN=dN, N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver)
+        values[:, run] = [member[:, 0] for member in obs[:-1]]
+        status[run] = obs.status[:, 0]
+    status = status.reshape(N0, N1)
+    obs = Observables(*values.reshape(-1, N0, N1), status)
+    return (obs, state, n_end, status) if return_status else (obs, state, n_end)

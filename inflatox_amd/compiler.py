@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -364,6 +364,16 @@ class CompilationArtifact:
                      ("INFLX_MASS_HEADER", "md{key}.mass.h", self.masses_header_text())],
         )  # fmt: skip
 
+    def ensure_tensor(self) -> str:
+        """Extension: build the tensor code object of this model -- the kernels of ``inflatox_amd.background.tensor_spectra``
+        (csrc/inflx_tensor_kernels.hip) -- and return its path, ``shared_object_path + ".tensor"``, where ``libinflx_hip.so`` looks
+        for it.  One hipcc step on first use from the core object's header and options and the header of the equations of motion
+        (no kinematics and no masses header: a tensor mode sees the background alone), cached as ``<tag>.tn<hash>.hsaco`` (the hash
+        covers the generated header and ``_TENSOR_SOURCES``, code only -- csrc/inflx_background.h among them, whose stepper pieces the
+        kernels reuse); the object carries the core object's ``MODEL_TAG`` and a layout word of its own (``INFLX_TN_ABI``).  Like the
+        other five companion objects it lies outside the kernel groups, and none of them is involved."""
+        return self._ensure_companion("tensor", _TENSOR_SOURCES, "tn{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "tn{key}.eom.h", self.eom_header_text())])
+
     def ensure_rowpass(self) -> str | None:
         """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
         evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
@@ -489,6 +499,7 @@ _KINEMATICS_SOURCES = ("inflx_kinematics_kernels.hip", "inflx_kinematics.h", "in
 _MASSES_SOURCES = ("inflx_masses_kernels.hip", "inflx_masses.h", "inflx_masses_abi.h")
 _TRANSFER_SOURCES = ("inflx_transfer_kernels.hip", "inflx_transfer.h", "inflx_transfer_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _MODES_SOURCES = ("inflx_modes_kernels.hip", "inflx_modes.h", "inflx_modes_abi.h", "inflx_background.h", "inflx_background_abi.h")
+_TENSOR_SOURCES = ("inflx_tensor_kernels.hip", "inflx_tensor.h", "inflx_tensor_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 

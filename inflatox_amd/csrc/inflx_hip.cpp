@@ -45,6 +45,7 @@
 #include "inflx_masses_abi.h"
 #include "inflx_transfer_abi.h"
 #include "inflx_modes_abi.h"
+#include "inflx_tensor_abi.h"
 
 namespace {
 
@@ -469,6 +470,10 @@ struct inflx_model {
   hipModule_t md_module = nullptr;
   hipFunction_t md_init = nullptr;
   hipFunction_t md_advance[2] = {};  // [method]
+  // tensor modes (inflx_mode_spectra with INFLX_MODES_TENSOR): the object `<artefact>.tensor`, loaded on first use
+  hipModule_t tn_module = nullptr;
+  hipFunction_t tn_init = nullptr;
+  hipFunction_t tn_advance[2] = {};  // [method]
 };
 
 namespace {
@@ -1385,6 +1390,7 @@ void inflx_close(inflx_model* m) {
   if (m->mass_module) (void)hipModuleUnload(m->mass_module);
   if (m->tr_module) (void)hipModuleUnload(m->tr_module);
   if (m->md_module) (void)hipModuleUnload(m->md_module);
+  if (m->tn_module) (void)hipModuleUnload(m->tn_module);
   if (m->module) (void)hipModuleUnload(m->module);
   delete m;
 }
@@ -3733,6 +3739,49 @@ int need_modes(inflx_model* m) {
   return INFLX_OK;
 }
 
+static_assert(kAbiMajor == INFLX_TN_DEFAULT_ABI_MAJOR, "a tensor object reports the core object's ABI major: change both together");
+
+// Load `<artefact>.tensor` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
+int need_tensor(inflx_model* m) {
+  if (m->tn_module) return INFLX_OK;
+  const std::string path = m->path + ".tensor";
+  FILE* fh = fopen(path.c_str(), "rb");
+  if (!fh)
+    return fail(INFLX_ERR_SYMBOL, "the tensor-mode kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_tensor() "
+                "(inflatox_amd.background.tensor_spectra does on first use)", m->path.c_str(), path.c_str());
+  fclose(fh);
+  HIP_TRY(hipSetDevice(m->device));
+  hipModule_t module = nullptr;
+  hipError_t e = hipModuleLoad(&module, path.c_str());
+  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
+  auto bail = [&](int code) {
+    const std::string first = g_last_error;
+    (void)hipModuleUnload(module);
+    g_last_error = first;
+    return code;
+  };
+  uint16_t version[3] = {};
+  uint32_t abi = 0;
+  char tag[128] = {0};
+  int rc;
+  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_TN_ABI", &abi, sizeof abi, true)) ||
+      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
+    return bail(rc);
+  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_TN_ABI_VERSION || m->tag != tag)
+    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
+                     "INFLX_TN_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_TN_ABI_VERSION));
+  const char* names[2] = {"inflx_tn_advance_rk4", "inflx_tn_advance_rkf"};
+  hipFunction_t init = nullptr, adv[2] = {};
+  if (hipModuleGetFunction(&init, module, "inflx_tn_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_tn_init", path.c_str()));
+  for (int a = 0; a < 2; ++a)
+    if (hipModuleGetFunction(&adv[a], module, names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a]));
+  m->tn_module = module;
+  m->tn_init = init;
+  for (int a = 0; a < 2; ++a) m->tn_advance[a] = adv[a];
+  note_sf_word(m, module);
+  return INFLX_OK;
+}
+
 // device buffers of one call, released on every way out
 struct MdBuffers {
   double *p = nullptr, *init = nullptr, *kappa = nullptr, *target = nullptr, *carry = nullptr, *out = nullptr;
@@ -3744,52 +3793,43 @@ struct MdBuffers {
   }
 };
 
-}  // namespace
+// the layouts of the two kinds of lane inflx_mode_spectra runs (csrc/inflx_modes_abi.h, csrc/inflx_tensor_abi.h)
+struct MdLayout {
+  using Args = InflxMdArgs;
+  static constexpr size_t kThreads = INFLX_MD_THREADS, kOutPlanes = INFLX_MD_OUT_PLANES, kCarryPlanes = INFLX_MD_CARRY_PLANES, kCarryNend = INFLX_MD_CARRY_NEND,
+                          kCarryStatus = INFLX_MD_CARRY_STATUS;
+};
+struct TnLayout {
+  using Args = InflxTnArgs;
+  static constexpr size_t kThreads = INFLX_TN_THREADS, kOutPlanes = INFLX_TN_OUT_PLANES, kCarryPlanes = INFLX_TN_CARRY_PLANES, kCarryNend = INFLX_TN_CARRY_NEND,
+                          kCarryStatus = INFLX_TN_CARRY_STATUS;
+};
 
-extern "C" {
-
-int inflx_mode_spectra(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* kappa, const double* n_target,
-                       size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status) {
-  INFLX_SERIALISE(m);
-  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the mode functions require a 2-field model (model has %u fields)", m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u parameters (got %zu)", m->name.c_str(), m->n_par, n_p);
-  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
-  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per lane (%zu)", P, B);
-  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
-  if (flags & ~(unsigned)INFLX_EOM_STOP_AT_END) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
-  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
-  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
-  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
-  if (B == 0) return INFLX_OK;
-  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
-  if (!kappa) return fail(INFLX_ERR_ARG, "kappa array is NULL");
-  if (!n_target) return fail(INFLX_ERR_ARG, "n_target array is NULL");
-  if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
-  HIP_TRY(hipSetDevice(m->device));
-  int rc = need_modes(m);
-  if (rc) return rc;
+// The passes, launches and read-back of inflx_mode_spectra over lanes of layout L, with the init kernel and the advance kernel of
+// the chosen method; the arguments are checked and the object is loaded.
+template <class L>
+int run_mode_lanes(inflx_model* m, hipFunction_t init_fn, hipFunction_t advance, const double* p, size_t P, size_t n_p, const double* init, size_t B,
+                   const double* kappa, const double* n_target, size_t max_steps, double max_err, double dt, unsigned flags, double* out, double* efolds,
+                   int8_t* status) {
   hipStream_t s = m->stream;
-  size_t nc_max = std::max<size_t>(1, kBgRowBytes / (INFLX_MD_OUT_PLANES * sizeof(double)));
-  if (nc_max > INFLX_MD_THREADS) nc_max -= nc_max % INFLX_MD_THREADS;
+  size_t nc_max = std::max<size_t>(1, kBgRowBytes / (L::kOutPlanes * sizeof(double)));
+  if (nc_max > L::kThreads) nc_max -= nc_max % L::kThreads;
   nc_max = std::min({B, kBgMaxLanes, nc_max});
-  constexpr size_t kBack = INFLX_MD_CARRY_PLANES - INFLX_MD_CARRY_NEND;  // the carry planes read back: NEND, STATUS
+  constexpr size_t kBack = L::kCarryPlanes - L::kCarryNend;  // the carry planes read back: NEND, STATUS
   MdBuffers buf;
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
   if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.kappa), nc_max * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.target), nc_max * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_MD_CARRY_PLANES * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), nc_max * INFLX_MD_OUT_PLANES * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * L::kCarryPlanes * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), nc_max * L::kOutPlanes * sizeof(double)));
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
   std::vector<double> host_carry(nc_max * kBack);
-  hipFunction_t advance = m->md_advance[method == INFLX_EOM_RKF ? 1 : 0];
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
-    InflxMdArgs a;
+    typename L::Args a;
     memset(&a, 0, sizeof a);
     a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
     a.p_stride = P == 1 ? 0 : n_p;
@@ -3804,36 +3844,71 @@ int inflx_mode_spectra(inflx_model* m, const double* p, size_t P, size_t n_p, co
     a.max_err = max_err;
     a.fixed_dt = dt;
     void* params[] = {&a};
-    const unsigned grid = (unsigned)((n + INFLX_MD_THREADS - 1) / INFLX_MD_THREADS);
+    const unsigned grid = (unsigned)((n + L::kThreads - 1) / L::kThreads);
     HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(buf.kappa, kappa + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(buf.target, n_target + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
     // every byte 0xff: each double is a NaN, which a lane that emits nothing keeps
-    HIP_TRY(hipMemsetAsync(buf.out, 0xff, n * INFLX_MD_OUT_PLANES * sizeof(double), s));
-    HIP_TRY(hipModuleLaunchKernel(m->md_init, grid, 1, 1, INFLX_MD_THREADS, 1, 1, 0, s, params, nullptr));
+    HIP_TRY(hipMemsetAsync(buf.out, 0xff, n * L::kOutPlanes * sizeof(double), s));
+    HIP_TRY(hipModuleLaunchKernel(init_fn, grid, 1, 1, L::kThreads, 1, 1, 0, s, params, nullptr));
     // launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
     for (uint64_t step = 0; step < (uint64_t)max_steps;) {
       const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
       a.steps = (uint32_t)k;
       uint32_t running = 0;
       HIP_TRY(hipMemsetAsync(buf.running, 0, sizeof(uint32_t), s));
-      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, INFLX_MD_THREADS, 1, 1, 0, s, params, nullptr));
+      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, L::kThreads, 1, 1, 0, s, params, nullptr));
       HIP_TRY(hipMemcpyAsync(&running, buf.running, sizeof running, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       step += k;
       if (running == 0) break;
     }
     // the planes as they are: a plane of this pass's lanes is n doubles, B doubles apart in `out`
-    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.out, n * sizeof(double), n * sizeof(double), INFLX_MD_OUT_PLANES, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry + (size_t)INFLX_MD_CARRY_NEND * n, n * kBack * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.out, n * sizeof(double), n * sizeof(double), L::kOutPlanes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry + (size_t)L::kCarryNend * n, n * kBack * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
-      status[c0 + l] = (int8_t)hc[(INFLX_MD_CARRY_STATUS - INFLX_MD_CARRY_NEND) * n + l];
+      status[c0 + l] = (int8_t)hc[(L::kCarryStatus - L::kCarryNend) * n + l];
       if (efolds) efolds[c0 + l] = hc[l];
     }
   }
   return sf_verdict(m);
+}
+
+}  // namespace
+
+extern "C" {
+
+int inflx_mode_spectra(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* kappa, const double* n_target,
+                       size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status) {
+  INFLX_SERIALISE(m);
+  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the mode functions require a 2-field model (model has %u fields)", m->dim);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u parameters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
+  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per lane (%zu)", P, B);
+  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
+  if (flags & ~(unsigned)(INFLX_EOM_STOP_AT_END | INFLX_MODES_TENSOR)) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
+  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
+  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
+  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  if (!kappa) return fail(INFLX_ERR_ARG, "kappa array is NULL");
+  if (!n_target) return fail(INFLX_ERR_ARG, "n_target array is NULL");
+  if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  const int mi = method == INFLX_EOM_RKF ? 1 : 0;
+  if (flags & INFLX_MODES_TENSOR) {
+    const int rc = need_tensor(m);
+    if (rc) return rc;
+    return run_mode_lanes<TnLayout>(m, m->tn_init, m->tn_advance[mi], p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
+  }
+  int rc = need_modes(m);
+  if (rc) return rc;
+  return run_mode_lanes<MdLayout>(m, m->md_init, m->md_advance[mi], p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
 }
 
 }  // extern "C"
