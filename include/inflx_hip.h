@@ -669,4 +669,8 @@ int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p
 #ifdef __cplusplus
 }
 #endif
+
+/* the delta-N expansion (derivatives of N with respect to the initial fields, local f_NL): its entry point is declared in a header of its own */
+#include "inflx_hip_deltan.h"
+
 #endif /* INFLX_HIP_H */

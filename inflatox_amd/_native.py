@@ -135,6 +135,17 @@ SIGNATURES = {
     ),
 }
 
+# the same for include/inflx_hip_deltan.h, the part of the C ABI that inflx_hip.h includes from a header of its own
+DELTAN_SIGNATURES = {
+    "inflx_delta_n": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, C.c_int, C.c_double, C.c_double, _DP, _SIZE, C.c_int, C.c_double, C.c_double, _DP, _DP, C.POINTER(C.c_int32)],
+    ),
+}
+DN_FIXED, DN_SLOW_ROLL, DN_EXPLICIT = 0, 1, 2  # inflx_dn_velocity
+DN_LOCATED, DN_PAST_SURFACE = 7, 8  # inflx_dn_status
+DN_OUT_PLANES = 21
+
 
 class Summary(C.Structure):
     """``inflx_summary``: NaN-ignoring min / max and the non-NaN count of the six outputs."""
@@ -147,7 +158,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -203,7 +214,7 @@ def load_library():
             )
         _preload_hip_runtime()
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -662,6 +673,37 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return out, efolds, status
+
+    # ---- delta-N stencils (include/inflx_hip_deltan.h: inflx_delta_n) -----------------------------
+    def delta_n(self, p, centre, vel, rule: int, h0: float, h1: float, h_end, max_steps: int, method: int, max_err: float, dt: float):
+        """B stencils of nine trajectories around ``centre`` (B,4), the members' velocities by ``rule`` (``DN_FIXED``, ``DN_SLOW_ROLL``,
+        or ``DN_EXPLICIT`` with ``vel`` (B,9,2)); ``h_end`` (B,) or None (phase A finds the surface).  Returns (out (21, B): the nine
+        N, N_,I, N_,IJ, N_;IJ, |grad N|^2, f_NL, P_zeta, status, stencil fastest; surface (2, B): H_c, N_c; status (int32)).  The
+        delta-N object must be in place (``CompilationArtifact.ensure_deltan``)."""
+        centre = _f64(centre, "centre")
+        p = _f64(p, "p")
+        B = centre.shape[0]
+        if vel is not None:
+            vel = _f64(vel, "vel")
+            if vel.shape != (B, 9, 2):
+                raise InflatoxShapeError(f"vel must have shape ({B}, 9, 2) (got {vel.shape})")
+        if h_end is not None:
+            h_end = _f64(h_end, "h_end")
+            if h_end.shape != (B,):
+                raise InflatoxShapeError(f"h_end must have shape ({B},) (got {h_end.shape})")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((DN_OUT_PLANES, B))
+        surface = np.empty((2, B))
+        status = np.empty(B, dtype=np.int32)
+        _check(
+            self._lib.inflx_delta_n(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(centre), B, None if vel is None else _ptr(vel), int(rule), float(h0), float(h1),
+                None if h_end is None else _ptr(h_end), int(max_steps), int(method), float(max_err), float(dt), _ptr(out), _ptr(surface),
+                status.ctypes.data_as(C.POINTER(C.c_int32)),
+            )
+        )  # fmt: skip
+        return out, surface, status
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

@@ -23,6 +23,9 @@ horizon exit -- and ``spectrum_map`` is ``horizon_exit_map`` followed by it.  ``
 spectrum P_T from one complex tensor amplitude per lane; ``observables`` differences both in ln k around a pivot of the trajectory's
 own -- the scalar tilt n_s, its running, the tensor tilt n_t and the tensor-to-scalar ratio r -- and ``observables_map`` is
 ``horizon_exit_map`` followed by it: n_s and r, as maps, of the mode that leaves the horizon N_star e-folds before the end of inflation.
+``delta_N`` runs nine-trajectory stencils around given states to one surface of uniform density each and differences the e-fold counts
+-- N_,I, N_,IJ, the covariant second derivative and the local non-Gaussianity f_NL of the delta-N expansion -- and ``fnl_map`` is
+``horizon_exit_map`` followed by it.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -48,12 +51,15 @@ from .compiler import CompilationArtifact
 
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
            "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses", "transfer_functions", "transfer_map",
-           "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra", "tensor_spectra", "TensorSpectra", "observables", "Observables", "observables_map"]  # fmt: skip
+           "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra", "tensor_spectra", "TensorSpectra", "observables", "Observables", "observables_map",
+           "delta_N", "DeltaN", "fnl_map", "delta_N_status"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
 #: ``horizon_exit_map`` only (no kernel status): inflation ended, but after fewer than N_star e-folds
 ENDED_SHORT = 6
+#: ``delta_N`` only (csrc/inflx_deltan.h): the trajectory met its surface / started at or past it
+LOCATED, PAST_SURFACE = 7, 8
 STATUS = {
     COMPLETE: "every requested step was taken",
     ENDED: "epsilon_H reached 1 (stop_at_end)",
@@ -62,6 +68,8 @@ STATUS = {
     UNDERFLOW: "the step size no longer moves t",
     TARGET: "N reached its target (state_at_efolds, horizon_exit_map); every sample was emitted (solve_eom_sampled)",
     ENDED_SHORT: "epsilon_H reached 1 after fewer than N_star e-folds (horizon_exit_map)",
+    LOCATED: "the trajectory met its surface of uniform density (delta_N)",
+    PAST_SURFACE: "the initial H is already at or below the surface's (delta_N)",
 }
 _METHODS = {"rk4": _native.EOM_RK4, "rkf": _native.EOM_RKF}
 
@@ -1063,3 +1071,155 @@ def observables_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1
     status = status.reshape(N0, N1)
     obs = Observables(*values.reshape(-1, N0, N1), status)
     return (obs, state, n_end, status) if return_status else (obs, state, n_end)
+
+
+# ---- the delta-N expansion -------------------------------------------------------------------------------------------------------
+class DeltaN(NamedTuple):
+    """What :func:`delta_N` returns, for B stencils.  ``N`` (B,): the centre's e-folds to the surface; ``H_end`` (B,): H on the surface;
+    ``N_members`` (B, 3, 3): N of the member at the centre's fields plus ((i - 1) h_0, (j - 1) h_1); ``N_I`` (B, 2) and ``N_IJ``
+    (B, 2, 2): the central differences N_,I and N_,IJ; ``N_cov`` (B, 2, 2): N_;IJ = N_,IJ - Gamma^K_IJ N_,K; ``grad2`` (B,):
+    G^IJ N_,I N_,J; ``f_NL`` (B,): (5/6) N^;I N^;J N_;IJ / grad2^2; ``P_zeta`` (B,): (H / 2 pi)^2 grad2 with the centre's initial H;
+    ``status`` (B,) int16: ``LOCATED`` where all nine members met the surface.  Elsewhere every member from ``N_I`` on is NaN
+    (``N_members`` keeps what was found) and ``status`` = s + 16 m (:func:`delta_N_status`): the status s of the lowest member
+    m = 3 i + j that failed -- ``COMPLETE``: ``max_steps`` ran out; ``PAST_SURFACE`` -- or, with m = 4, of the centre's search for the
+    end of inflation."""
+
+    N: np.ndarray
+    H_end: np.ndarray
+    N_members: np.ndarray
+    N_I: np.ndarray
+    N_IJ: np.ndarray
+    N_cov: np.ndarray
+    grad2: np.ndarray
+    f_NL: np.ndarray
+    P_zeta: np.ndarray
+    status: np.ndarray
+
+
+_VELOCITY_RULES = {"fixed": _native.DN_FIXED, "slow_roll": _native.DN_SLOW_ROLL}
+
+
+def delta_N_status(status):
+    """(code, member) of a :class:`DeltaN` status: the ``STATUS`` code and the index m = 3 i + j of the member it belongs to (0 for
+    ``LOCATED``)."""
+    status = np.asarray(status)
+    return status % 16, status // 16
+
+
+def _check_delta_n_options(artifact, h, velocity, max_steps, max_err, solver, dt):
+    """The checks ``delta_N`` and ``fnl_map`` share: (h0, h1, max_steps, max_err, dt)."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    try:
+        hh = np.asarray(h, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("h must be a number or a pair of numbers") from None
+    if hh.shape not in ((), (2,)):
+        raise InflatoxShapeError(f"h must be a scalar or a pair (got shape {hh.shape})")
+    h0, h1 = (float(v) for v in np.broadcast_to(hh, (2,)))
+    if not (math.isfinite(h0) and h0 > 0.0 and math.isfinite(h1) and h1 > 0.0):
+        raise ValueError(f"h must be positive and finite (got {h})")
+    if velocity not in _VELOCITY_RULES:
+        raise ValueError(f"unknown velocity rule {velocity!r}: choose 'fixed' or 'slow_roll' (or pass derivatives_init of shape (B, 3, 3, 2))")
+    return h0, h1, max_steps, max_err, dt
+
+
+def _check_delta_n(artifact, pars, fields_init, derivatives_init, h, velocity, H_end, max_steps, max_err, solver, dt):
+    """The argument checks of ``delta_N``: (p, centre (B, 4), vel (B, 9, 2) or None, rule, h0, h1, h_end (B,) or None, max_steps,
+    max_err, dt)."""
+    h0, h1, max_steps, max_err, dt = _check_delta_n_options(artifact, h, velocity, max_steps, max_err, solver, dt)
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise InflatoxShapeError(f"fields_init must have shape (B, 2) (got {x.shape})")
+    B = x.shape[0]
+    rule, vel = _VELOCITY_RULES[velocity], None
+    if derivatives_init is None:
+        if velocity == "fixed":
+            raise ValueError("velocity='fixed' needs derivatives_init, the centres' coordinate velocities")
+        v = np.zeros_like(x)
+    else:
+        v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+        if v.ndim == 4:
+            if v.shape != (B, 3, 3, 2):
+                raise InflatoxShapeError(f"explicit member velocities must have shape ({B}, 3, 3, 2) (got {v.shape})")
+            rule, vel = _native.DN_EXPLICIT, np.ascontiguousarray(v.reshape(B, 9, 2))
+            v = np.ascontiguousarray(v[:, 1, 1])
+        elif v.shape != x.shape:
+            raise InflatoxShapeError(f"derivatives_init must have shape ({B}, 2) or ({B}, 3, 3, 2) (got {v.shape})")
+    h_end = None
+    if H_end is not None:
+        try:
+            h_end = np.ascontiguousarray(np.broadcast_to(np.asarray(H_end, dtype=np.float64), (B,)))
+        except (TypeError, ValueError):
+            raise ValueError(f"H_end must be None, a number or an array of shape ({B},)") from None
+        if not (np.isfinite(h_end).all() and (h_end > 0.0).all()):
+            raise ValueError("H_end must be positive and finite")
+    p = _pars(artifact, pars, B)
+    return p, np.concatenate([x, v], axis=1), vel, rule, h0, h1, h_end, max_steps, max_err, dt
+
+
+def _delta_n_result(out, surface, status) -> DeltaN:
+    B = out.shape[1]
+    n_ij = np.stack([out[11], out[13], out[13], out[12]], axis=1).reshape(B, 2, 2)
+    n_cov = np.stack([out[14], out[16], out[16], out[15]], axis=1).reshape(B, 2, 2)
+    return DeltaN(out[4], surface[0], out[:9].T.reshape(B, 3, 3), out[9:11].T, n_ij, n_cov, out[17], out[18], out[19], status.astype(np.int16))
+
+
+def delta_N(artifact: CompilationArtifact, pars, fields_init, derivatives_init=None, *, h=1e-2, velocity: str = "fixed", H_end=None,
+            max_steps: int = 1_000_000, max_err: float = 1e-10, solver: str = "rkf", dt: float | None = None) -> DeltaN:  # fmt: skip
+    """First and second derivatives of the e-fold count with respect to the initial fields, and the local f_NL of the delta-N
+    expansion zeta = N_,I dphi^I + N_,IJ dphi^I dphi^J / 2, around each of the B states ``fields_init`` (B, 2).
+
+    What is differentiated is N(phi; chi(phi)): the e-folds of the trajectory that starts at the fields phi with the velocity that the
+    chosen rule gives it there, counted to a surface of uniform density -- the surface H = H_c through the point of the CENTRE's
+    trajectory where epsilon_H = 1, or H = ``H_end`` (a number or (B,)) when that is given, which a model whose inflation never ends
+    needs.  The rules: ``velocity="fixed"`` gives every member of a stencil the centre's coordinate velocity ``derivatives_init``
+    (B, 2); ``"slow_roll"`` gives each, the centre included, chi^a = -G^ab d_b V / (3 H) with H^2 = V / 3 at its own fields
+    (``derivatives_init`` is not needed); a ``derivatives_init`` of shape (B, 3, 3, 2) gives every member its velocity explicitly.
+    ``"fixed"`` and ``"slow_roll"`` are approximations to the attractor, not the attractor: on a trajectory that has not settled, or
+    turns sharply at the start, the derivatives carry the difference, and only explicit velocities taken from neighbouring
+    attractor solutions remove it.
+
+    Each stencil is nine trajectories at the offsets (i - 1) ``h``[0], (j - 1) ``h``[1] in field coordinates (``h``: a number or a
+    pair), one GPU lane each with the step control of ``solve_eom_batch``; both events are located on the integrator's cubic dense
+    output, so N of a member is as accurate as its trajectory (DESIGN.md section 12 has the measured figures: the differences are
+    limited by ``max_err``, and by h^2 truncation).  ``pars`` is one row or (B, n): stencil b uses row b for all its members.  Metric
+    and connection in the covariant formulas are those at the centre.  The kernels are csrc/inflx_deltan_kernels.hip, built into
+    ``<artefact>.deltan`` on first use (``CompilationArtifact.ensure_deltan``).  Returns a :class:`DeltaN`."""
+    p, centre, vel, rule, h0, h1, h_end, max_steps, max_err, dt = _check_delta_n(artifact, pars, fields_init, derivatives_init, h, velocity, H_end, max_steps, max_err,
+                                                                                 solver, dt)  # fmt: skip
+    artifact.ensure_deltan()
+    out, surface, status = _dylib(artifact, background=False).delta_n(p, centre, vel, rule, h0, h1, h_end, max_steps, _METHODS[solver], max_err, dt or 0.0)
+    return _delta_n_result(out, surface, status)
+
+
+def fnl_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N_star: float = 55.0, h=1e-2, velocity: str = "fixed",
+            derivatives_init=(0.0, 0.0), max_steps: int = 1_000_000, max_err: float = 1e-10, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """``horizon_exit_map`` (same arguments) followed by ``delta_N`` from every exit state to the end of inflation: ``(dn, state,
+    N_end)`` with ``dn`` the :class:`DeltaN` of (N0, N1, ...) arrays -- f_NL and the derivatives of N of the mode that leaves the
+    horizon ``N_star`` e-folds before the end of inflation, from the trajectory of every grid point -- and ``state`` (N0, N1, 5) and
+    ``N_end`` (N0, N1) exactly ``horizon_exit_map``'s.  With ``velocity="fixed"`` the members of a stencil take the exit state's
+    velocity; with ``"slow_roll"`` each takes its own slow-roll velocity.  H starts again from the Friedmann constraint.  NaN where no
+    exit state was found; ``dn.status`` and, with ``return_status=True``, a fourth member are the (N0, N1) int16 status map:
+    ``horizon_exit_map``'s, with ``delta_N``'s status (``LOCATED`` where the values are valid) in place of ``TARGET``."""
+    _check_delta_n_options(artifact, h, velocity, max_steps, max_err, solver, None)
+    try:
+        N_star = float(N_star)
+    except (TypeError, ValueError):
+        raise ValueError("N_star must be a number") from None
+    if not (math.isfinite(N_star) and N_star >= 0.0):
+        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
+    N0, N1 = n_end.shape
+    flat = state.reshape(-1, 5)
+    status = status.astype(np.int16).reshape(-1)
+    shapes = {"N_members": (3, 3), "N_I": (2,), "N_IJ": (2, 2), "N_cov": (2, 2)}
+    values = {name: np.full((N0 * N1, *shapes.get(name, ())), np.nan) for name in DeltaN._fields[:-1]}
+    run = np.flatnonzero(status == TARGET)
+    if run.size:
+        dn = delta_N(artifact, pars, flat[run, :2], flat[run, 2:4], h=h, velocity=velocity, max_steps=max_steps, max_err=max_err, solver=solver)
+        for name in values:
+            values[name][run] = getattr(dn, name)
+        status[run] = dn.status
+    status = status.reshape(N0, N1)
+    dn = DeltaN(*(values[name].reshape(N0, N1, *shapes.get(name, ())) for name in DeltaN._fields[:-1]), status)
+    return (dn, state, n_end, status) if return_status else (dn, state, n_end)

@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -374,6 +374,16 @@ class CompilationArtifact:
         other five companion objects it lies outside the kernel groups, and none of them is involved."""
         return self._ensure_companion("tensor", _TENSOR_SOURCES, "tn{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "tn{key}.eom.h", self.eom_header_text())])
 
+    def ensure_deltan(self) -> str:
+        """Extension: build the delta-N code object of this model -- the kernels of ``inflatox_amd.background.delta_N``
+        (csrc/inflx_deltan_kernels.hip) -- and return its path, ``shared_object_path + ".deltan"``, where ``libinflx_hip.so`` looks
+        for it.  One hipcc step on first use from the core object's header and options and the header of the equations of motion,
+        cached as ``<tag>.dn<hash>.hsaco`` (the hash covers the generated header and ``_DELTAN_SOURCES``, code only --
+        csrc/inflx_background.h among them, whose stepper the kernels run); the object carries the core object's ``MODEL_TAG`` and a
+        layout word of its own (``INFLX_DN_ABI``).  Like the other six companion objects it lies outside the kernel groups, and none
+        of them is involved."""
+        return self._ensure_companion("deltan", _DELTAN_SOURCES, "dn{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "dn{key}.eom.h", self.eom_header_text())])
+
     def ensure_rowpass(self) -> str | None:
         """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
         evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
@@ -500,6 +510,7 @@ _MASSES_SOURCES = ("inflx_masses_kernels.hip", "inflx_masses.h", "inflx_masses_a
 _TRANSFER_SOURCES = ("inflx_transfer_kernels.hip", "inflx_transfer.h", "inflx_transfer_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _MODES_SOURCES = ("inflx_modes_kernels.hip", "inflx_modes.h", "inflx_modes_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _TENSOR_SOURCES = ("inflx_tensor_kernels.hip", "inflx_tensor.h", "inflx_tensor_abi.h", "inflx_background.h", "inflx_background_abi.h")
+_DELTAN_SOURCES = ("inflx_deltan_kernels.hip", "inflx_deltan.h", "inflx_deltan_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 

@@ -25,6 +25,7 @@
 #include <cstring>
 #include <mutex>
 #include <future>
+#include <limits>
 #include <random>
 #include <string>
 #include <thread>
@@ -46,6 +47,7 @@
 #include "inflx_transfer_abi.h"
 #include "inflx_modes_abi.h"
 #include "inflx_tensor_abi.h"
+#include "inflx_deltan_abi.h"
 
 namespace {
 
@@ -474,6 +476,10 @@ struct inflx_model {
   hipModule_t tn_module = nullptr;
   hipFunction_t tn_init = nullptr;
   hipFunction_t tn_advance[2] = {};  // [method]
+  // delta-N stencils (inflx_delta_n): the object `<artefact>.deltan`, loaded on first use
+  hipModule_t dn_module = nullptr;
+  hipFunction_t dn_init = nullptr, dn_reduce = nullptr;
+  hipFunction_t dn_end[2] = {}, dn_surface[2] = {};  // [method]: phase A, phase B
 };
 
 namespace {
@@ -1391,6 +1397,7 @@ void inflx_close(inflx_model* m) {
   if (m->tr_module) (void)hipModuleUnload(m->tr_module);
   if (m->md_module) (void)hipModuleUnload(m->md_module);
   if (m->tn_module) (void)hipModuleUnload(m->tn_module);
+  if (m->dn_module) (void)hipModuleUnload(m->dn_module);
   if (m->module) (void)hipModuleUnload(m->module);
   delete m;
 }
@@ -3909,6 +3916,196 @@ int inflx_mode_spectra(inflx_model* m, const double* p, size_t P, size_t n_p, co
   int rc = need_modes(m);
   if (rc) return rc;
   return run_mode_lanes<MdLayout>(m, m->md_init, m->md_advance[mi], p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
+}
+
+}  // extern "C"
+
+// ---- delta-N stencils: derivatives of N and local f_NL (inflx_delta_n) -------------------------------------------------------------
+namespace {
+
+static_assert(kAbiMajor == INFLX_DN_DEFAULT_ABI_MAJOR, "a delta-N object reports the core object's ABI major: change both together");
+
+// Load `<artefact>.deltan` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
+int need_deltan(inflx_model* m) {
+  if (m->dn_module) return INFLX_OK;
+  const std::string path = m->path + ".deltan";
+  FILE* fh = fopen(path.c_str(), "rb");
+  if (!fh)
+    return fail(INFLX_ERR_SYMBOL, "the delta-N kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_deltan() "
+                "(inflatox_amd.background.delta_N does on first use)", m->path.c_str(), path.c_str());
+  fclose(fh);
+  HIP_TRY(hipSetDevice(m->device));
+  hipModule_t module = nullptr;
+  hipError_t e = hipModuleLoad(&module, path.c_str());
+  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
+  auto bail = [&](int code) {
+    const std::string first = g_last_error;
+    (void)hipModuleUnload(module);
+    g_last_error = first;
+    return code;
+  };
+  uint16_t version[3] = {};
+  uint32_t abi = 0;
+  char tag[128] = {0};
+  int rc;
+  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_DN_ABI", &abi, sizeof abi, true)) ||
+      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
+    return bail(rc);
+  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_DN_ABI_VERSION || m->tag != tag)
+    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
+                     "INFLX_DN_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_DN_ABI_VERSION));
+  const char* names[6] = {"inflx_dn_init", "inflx_dn_reduce", "inflx_dn_end_rk4", "inflx_dn_end_rkf", "inflx_dn_surface_rk4", "inflx_dn_surface_rkf"};
+  hipFunction_t fn[6] = {};
+  for (int a = 0; a < 6; ++a)
+    if (hipModuleGetFunction(&fn[a], module, names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a]));
+  m->dn_module = module;
+  m->dn_init = fn[0];
+  m->dn_reduce = fn[1];
+  for (int a = 0; a < 2; ++a) {
+    m->dn_end[a] = fn[2 + a];
+    m->dn_surface[a] = fn[4 + a];
+  }
+  note_sf_word(m, module);
+  return INFLX_OK;
+}
+
+// device buffers of one call, released on every way out
+struct DnBuffers {
+  double *p = nullptr, *centre = nullptr, *vel = nullptr, *carry_a = nullptr, *carry = nullptr, *hc = nullptr, *out = nullptr;
+  uint32_t* running = nullptr;
+  ~DnBuffers() {
+    for (double* d : {p, centre, vel, carry_a, carry, hc, out})
+      if (d) (void)hipFree(d);
+    if (running) (void)hipFree(running);
+  }
+};
+
+// launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
+int dn_advance(hipFunction_t fn, InflxDnArgs& a, size_t lanes, size_t max_steps, uint32_t* d_running, hipStream_t s) {
+  void* params[] = {&a};
+  const unsigned grid = (unsigned)((lanes + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS);
+  for (uint64_t step = 0; step < (uint64_t)max_steps;) {
+    const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
+    a.steps = (uint32_t)k;
+    uint32_t running = 0;
+    HIP_TRY(hipMemsetAsync(d_running, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
+    HIP_TRY(hipMemcpyAsync(&running, d_running, sizeof running, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    step += k;
+    if (running == 0) break;
+  }
+  return INFLX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int inflx_delta_n(inflx_model* m, const double* p, size_t P, size_t n_p, const double* centre, size_t B, const double* vel, int rule, double h0, double h1,
+                  const double* h_end, size_t max_steps, int method, double max_err, double dt, double* out, double* surface, int32_t* status) {
+  INFLX_SERIALISE(m);
+  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the delta-N expansion requires a 2-field model (model has %u fields)", m->dim);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u parameters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
+  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per stencil (%zu)", P, B);
+  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
+  if (rule != INFLX_DN_VELOCITY_FIXED && rule != INFLX_DN_VELOCITY_SLOW_ROLL && rule != INFLX_DN_VELOCITY_EXPLICIT) return fail(INFLX_ERR_ARG, "unknown velocity rule %d", rule);
+  if ((rule == INFLX_DN_VELOCITY_EXPLICIT) != (vel != nullptr) && B) return fail(INFLX_ERR_ARG, "the member velocities go with the explicit rule, and only with it");
+  if (!(h0 > 0.0) || !std::isfinite(h0) || !(h1 > 0.0) || !std::isfinite(h1)) return fail(INFLX_ERR_ARG, "the stencil steps must be positive finite numbers");
+  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
+  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
+  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  if (h_end)
+    for (size_t b = 0; b < B; ++b)
+      if (!(h_end[b] > 0.0) || !std::isfinite(h_end[b])) return fail(INFLX_ERR_ARG, "h_end %zu is not a positive finite number", b);
+  if (B == 0) return INFLX_OK;
+  if (!centre) return fail(INFLX_ERR_ARG, "centre array is NULL");
+  if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  int rc = need_deltan(m);
+  if (rc) return rc;
+  hipStream_t s = m->stream;
+  const int mi = method == INFLX_EOM_RKF ? 1 : 0;
+  // a pass holds whole stencils: its 9 nb lanes stay within the lane bound of a pass of the solver
+  const size_t nb_max = std::min(B, std::max<size_t>(1, kBgMaxLanes / 9));
+  DnBuffers buf;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
+  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.centre), nb_max * 4 * sizeof(double)));
+  if (vel) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.vel), nb_max * 18 * sizeof(double)));
+  if (!h_end) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry_a), nb_max * INFLX_DN_CARRY_PLANES * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nb_max * 9 * INFLX_DN_CARRY_PLANES * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.hc), nb_max * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), nb_max * INFLX_DN_OUT_PLANES * sizeof(double)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  std::vector<double> host_status(nb_max), host_surface(2 * nb_max);
+
+  for (size_t c0 = 0; c0 < B; c0 += nb_max) {
+    const size_t nb = std::min(nb_max, B - c0);
+    InflxDnArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.centre = buf.centre;
+    a.vel = buf.vel;
+    a.hc = buf.hc;
+    a.running = buf.running;
+    a.nb = nb;
+    a.rule = (uint32_t)rule;
+    a.h0 = h0;
+    a.h1 = h1;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    void* params[] = {&a};
+    HIP_TRY(hipMemcpyAsync(buf.centre, centre + c0 * 4, nb * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (vel) HIP_TRY(hipMemcpyAsync(buf.vel, vel + c0 * 18, nb * 18 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (h_end) {
+      HIP_TRY(hipMemcpyAsync(buf.hc, h_end + c0, nb * sizeof(double), hipMemcpyHostToDevice, s));
+    } else {
+      // phase A, the centres alone: every byte 0xff is a NaN, which a centre that finds no surface keeps
+      HIP_TRY(hipMemsetAsync(buf.hc, 0xff, nb * sizeof(double), s));
+      a.carry = buf.carry_a;
+      a.members = 1;
+      HIP_TRY(hipModuleLaunchKernel(m->dn_init, (unsigned)((nb + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
+      if ((rc = dn_advance(m->dn_end[mi], a, nb, max_steps, buf.running, s))) return rc;
+    }
+    // phase B, all nine members
+    const size_t lanes = 9 * nb;
+    a.carry = buf.carry;
+    a.members = 9;
+    HIP_TRY(hipModuleLaunchKernel(m->dn_init, (unsigned)((lanes + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
+    if ((rc = dn_advance(m->dn_surface[mi], a, lanes, max_steps, buf.running, s))) return rc;
+    InflxDnReduceArgs r;
+    memset(&r, 0, sizeof r);
+    r.p = a.p;
+    r.p_stride = a.p_stride;
+    r.centre = buf.centre;
+    r.carry = buf.carry;
+    r.status_a = h_end ? nullptr : buf.carry_a + (size_t)INFLX_DN_CARRY_STATUS * nb;
+    r.out = buf.out;
+    r.nb = nb;
+    r.h0 = h0;
+    r.h1 = h1;
+    void* rparams[] = {&r};
+    HIP_TRY(hipModuleLaunchKernel(m->dn_reduce, (unsigned)((nb + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, rparams, nullptr));
+    // the planes as they are: a plane of this pass's stencils is nb doubles, B doubles apart in `out`
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.out, nb * sizeof(double), nb * sizeof(double), INFLX_DN_OUT_PLANES, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_status.data(), buf.out + (size_t)(INFLX_DN_OUT_PLANES - 1) * nb, nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_surface.data(), buf.hc, nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (!h_end) HIP_TRY(hipMemcpyAsync(host_surface.data() + nb, buf.carry_a + (size_t)INFLX_DN_CARRY_RESULT * nb, nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t l = 0; l < nb; ++l) {
+      status[c0 + l] = (int32_t)host_status[l];
+      if (surface) {
+        surface[c0 + l] = host_surface[l];
+        surface[B + c0 + l] = h_end ? std::numeric_limits<double>::quiet_NaN() : host_surface[nb + l];
+      }
+    }
+  }
+  return sf_verdict(m);
 }
 
 }  // extern "C"
