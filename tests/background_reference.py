@@ -225,10 +225,12 @@ class BackgroundTwin:
     """tests/background_twin.cpp built for the CPU from an artefact's generated headers (contraction off: the twin's arithmetic is the
     restatement's, operation for operation)."""
 
-    def __init__(self, artifact, cxx: str = "g++"):
+    def __init__(self, artifact, cxx: str = "g++", contract: str = "off"):
+        """``contract="fast"`` lets the compiler fuse a*b+c into FMAs (the CPU must have them), as hipcc does for the kernels."""
         header_text = artifact._build[0]
         eom_text = artifact.eom_header_text()
-        tag = hashlib.sha1((header_text + eom_text + open(os.path.join(ROOT, "inflatox_amd", "csrc", "inflx_background.h")).read()).encode()).hexdigest()[:16]
+        background_h = open(os.path.join(ROOT, "inflatox_amd", "csrc", "inflx_background.h")).read()
+        tag = hashlib.sha1((header_text + eom_text + background_h + contract).encode()).hexdigest()[:16]
         d = os.path.join(tempfile.gettempdir(), "inflx_background_twin")
         os.makedirs(d, exist_ok=True)
         hdr, eom_hdr, so = (os.path.join(d, f"{tag}{s}") for s in (".h", ".eom.h", ".so"))
@@ -237,7 +239,7 @@ class BackgroundTwin:
                 with open(path, "w") as fh:
                     fh.write(text)
             cmd = [
-                cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unknown-pragmas",
+                cxx, "-O2", "-std=c++17", "-fPIC", "-shared", f"-ffp-contract={contract}", *(["-mfma"] if contract != "off" else []), "-fno-fast-math", "-Wno-unknown-pragmas",
                 f"-I{os.path.join(ROOT, 'inflatox_amd', 'csrc')}", f'-DINFLX_MODEL_HEADER="{hdr}"', f'-DINFLX_EOM_HEADER="{eom_hdr}"',
                 os.path.join(HERE, "background_twin.cpp"), "-o", so + ".tmp",
             ]  # fmt: skip
@@ -283,6 +285,27 @@ def power_law_artifact():
     p = np.zeros(art.n_parameters)
     p[int(art.symbol_dictionary["V0"][5:-1])] = V0
     p[int(art.symbol_dictionary["lam"][5:-1])] = LAM
+    return art, p
+
+
+# ---- a potential with a wall: V = V0 + m phi^(3/2) on a flat field space, finite at phi = 0 (V = V0, dV = 0), NaN for every phi < 0 --
+WALL_V0, WALL_M = 1.0, 1.0
+
+
+def wall_model():
+    from inflatox_amd import InflationModelBuilder
+
+    phi, theta, v0, m = sympy.symbols("phi theta V0 m")
+    return InflationModelBuilder.new([phi, theta], [[1, 0], [0, 1]], v0 + m * phi ** sympy.Rational(3, 2), model_name="wall", init_sympy_printing=False, silent=True).build()
+
+
+def wall_artifact():
+    from inflatox_amd import Compiler
+
+    art = Compiler(wall_model(), silent=True).compile()
+    p = np.zeros(art.n_parameters)
+    p[int(art.symbol_dictionary["V0"][5:-1])] = WALL_V0
+    p[int(art.symbol_dictionary["m"][5:-1])] = WALL_M
     return art, p
 
 
