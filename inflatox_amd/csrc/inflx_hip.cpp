@@ -39,6 +39,7 @@
 #include <unistd.h>
 
 #include "inflx_background_abi.h"
+#include "inflx_background_passes.h"
 #include "inflx_background_rows.h"
 #include "inflx_kernel_abi.h"
 #include "inflx_rowpass_abi.h"
@@ -366,6 +367,15 @@ struct TableRing {
   std::unique_lock<std::recursive_mutex> inflx_call_lock_; \
   if (m) inflx_call_lock_ = std::unique_lock<std::recursive_mutex>((m)->mu)
 
+// The code objects beside the core object that the background solver's families live in (kCompanions describes them), and what a
+// handle holds of one: its module and its kernels, in the order of the description's names.
+enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kCompanionCount };
+constexpr int kCompanionKernels = 10;  // the most kernels of one object (background)
+struct CompanionSlot {
+  hipModule_t module = nullptr;
+  hipFunction_t fn[kCompanionKernels] = {};
+};
+
 struct inflx_model {
   // Every entry point that works on a handle holds this lock for the call: a handle owns streams, staging buffers, the
   // parameter-slot ring and the double-buffered tables, none of which two calls may use at once.  (The reference holds the
@@ -451,35 +461,8 @@ struct inflx_model {
   hipEvent_t chunk_done[2] = {nullptr, nullptr};
   hipEvent_t copy_done[2] = {nullptr, nullptr};
   hipEvent_t t0 = nullptr, t1 = nullptr;
-  // background trajectories (inflx_solve_eom): the object `<artefact>.background`, loaded on first use
-  hipModule_t bg_module = nullptr;
-  hipFunction_t bg_init = nullptr;
-  hipFunction_t bg_advance[2][2] = {};  // [method][store rows]
-  hipFunction_t bg_target[2] = {};      // [method]: final-only with a target on N (inflx_solve_eom_to_efolds)
-  hipFunction_t bg_sampled[2] = {};     // [method]: final-only with a list of samples (inflx_solve_eom_sampled)
-  hipFunction_t bg_rows_transpose = nullptr;  // row planes -> (lanes, rows, 6) and (lanes, rows) (csrc/inflx_background_rows.h)
-  // trajectory kinematics (inflx_kinematics): the object `<artefact>.kinematics`, loaded on first use
-  hipModule_t kin_module = nullptr;
-  hipFunction_t kin_states = nullptr;
-  // entropic masses (inflx_masses): the object `<artefact>.masses`, loaded on first use
-  hipModule_t mass_module = nullptr;
-  hipFunction_t mass_states = nullptr;
-  // transfer functions (inflx_transfer_functions): the object `<artefact>.transfer`, loaded on first use
-  hipModule_t tr_module = nullptr;
-  hipFunction_t tr_init = nullptr;
-  hipFunction_t tr_advance[2] = {};  // [method]
-  // mode functions (inflx_mode_spectra): the object `<artefact>.modes`, loaded on first use
-  hipModule_t md_module = nullptr;
-  hipFunction_t md_init = nullptr;
-  hipFunction_t md_advance[2] = {};  // [method]
-  // tensor modes (inflx_mode_spectra with INFLX_MODES_TENSOR): the object `<artefact>.tensor`, loaded on first use
-  hipModule_t tn_module = nullptr;
-  hipFunction_t tn_init = nullptr;
-  hipFunction_t tn_advance[2] = {};  // [method]
-  // delta-N stencils (inflx_delta_n): the object `<artefact>.deltan`, loaded on first use
-  hipModule_t dn_module = nullptr;
-  hipFunction_t dn_init = nullptr, dn_reduce = nullptr;
-  hipFunction_t dn_end[2] = {}, dn_surface[2] = {};  // [method]: phase A, phase B
+  // the companion objects of the background solver, `<artefact>.<suffix>`, each loaded on first use (kCompanions, need_companion)
+  CompanionSlot companion[kCompanionCount];
 };
 
 namespace {
@@ -1390,14 +1373,9 @@ void inflx_close(inflx_model* m) {
   if (m->side) (void)hipStreamDestroy(m->side);
   if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
   for (hipModule_t extra : m->attached) (void)hipModuleUnload(extra);
-  if (m->bg_module) (void)hipModuleUnload(m->bg_module);
+  for (const CompanionSlot& slot : m->companion)
+    if (slot.module) (void)hipModuleUnload(slot.module);
   if (m->rowpass_module) (void)hipModuleUnload(m->rowpass_module);
-  if (m->kin_module) (void)hipModuleUnload(m->kin_module);
-  if (m->mass_module) (void)hipModuleUnload(m->mass_module);
-  if (m->tr_module) (void)hipModuleUnload(m->tr_module);
-  if (m->md_module) (void)hipModuleUnload(m->md_module);
-  if (m->tn_module) (void)hipModuleUnload(m->tn_module);
-  if (m->dn_module) (void)hipModuleUnload(m->dn_module);
   if (m->module) (void)hipModuleUnload(m->module);
   delete m;
 }
@@ -2912,21 +2890,66 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* mm, int op, const double* p, siz
 
 }  // extern "C"
 
-// ---- background trajectories (inflx_solve_eom) ------------------------------------------------------------------------------
+// ---- the background solver: what its families share ---------------------------------------------------------------------------
+// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N -- has its kernels in
+// a code object of its own beside the core object, `<artefact>.<suffix>`, which CompilationArtifact.ensure_<suffix>() builds.
+// kCompanions has one constant description per object: the words of its messages, its layout word, its kernels.  need_companion
+// loads any of them into its slot of the handle on first use, and a call site names a kernel by its family's index below.  The
+// entry points further share the checks of the integrator's arguments (check_integrator_args, check_samples), the launches that
+// advance a pass (advance_until_done), the lanes of a pass (inflx_bg_lanes_per_pass, csrc/inflx_background_passes.h; the bounds
+// kBgMaxLanes, kBgRowBytes and the plan of a row call's passes: csrc/inflx_background_rows.h) and the holder of a call's device
+// buffers (DeviceBuffers).
 namespace {
 
-// the kernels' argument block and the carry planes: csrc/inflx_background_abi.h
 static_assert(kAbiMajor == INFLX_BG_DEFAULT_ABI_MAJOR, "a background object reports the core object's ABI major: change both together");
-// bounds of one call's passes (kBgMaxLanes, kBgRowBytes) and the plan of a row call's passes: csrc/inflx_background_rows.h
+static_assert(kAbiMajor == INFLX_KIN_DEFAULT_ABI_MAJOR, "a kinematics object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_MASS_DEFAULT_ABI_MAJOR, "a masses object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_TR_DEFAULT_ABI_MAJOR, "a transfer object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_MD_DEFAULT_ABI_MAJOR, "a modes object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_TN_DEFAULT_ABI_MAJOR, "a tensor object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_DN_DEFAULT_ABI_MAJOR, "a delta-N object reports the core object's ABI major: change both together");
 
-// Load `<artefact>.background` beside the core object: it must carry the core object's MODEL_TAG.
-int need_background(inflx_model* m) {
-  if (m->bg_module) return INFLX_OK;
-  const std::string path = m->path + ".background";
+struct CompanionDesc {
+  const char* suffix;      // the file is `<artefact>.<suffix>` and CompilationArtifact.ensure_<suffix>() builds it
+  const char* label;       // "the <label> of <artefact> <verb> not loaded ..."
+  const char* verb;
+  const char* python;      // the Python function that builds it on first use
+  const char* abi_symbol;  // the object's layout word
+  uint32_t abi;            // ... and this library's value of it
+  const char* kernels[kCompanionKernels + 1];  // ends with a null
+};
+// the kernels of an object, by their place in its description; `+ method` is + 0 for INFLX_EOM_RK4 and + 1 for INFLX_EOM_RKF
+enum BgKernel { kBgInit, kBgRowsTranspose, kBgAdvance /* + 2 method + store rows */, kBgTarget = 6 /* + method */, kBgSampled = 8 /* + method */ };
+enum StateKernel { kStates };                                // kinematics, masses
+enum LaneKernel { kLaneInit, kLaneAdvance /* + method */ };  // transfer, modes, tensor
+enum DnKernel { kDnInit, kDnReduce, kDnEnd /* + method: phase A */, kDnSurface = 4 /* + method: phase B */ };
+const CompanionDesc kCompanions[kCompanionCount] = {
+    {"background", "background kernels", "are", "inflatox_amd.background", "INFLX_BG_ABI", INFLX_BG_ABI_VERSION,
+     {"inflx_bg_init", "inflx_bg_rows_transpose", "inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows", "inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows",
+      "inflx_bg_advance_rk4_target", "inflx_bg_advance_rkf_target", "inflx_bg_advance_rk4_sampled", "inflx_bg_advance_rkf_sampled"}},
+    {"kinematics", "kinematics kernel", "is", "inflatox_amd.background.kinematics", "INFLX_KIN_ABI", INFLX_KIN_ABI_VERSION, {"inflx_kin_states"}},
+    {"masses", "masses kernel", "is", "inflatox_amd.background.masses", "INFLX_MASS_ABI", INFLX_MASS_ABI_VERSION, {"inflx_mass_states"}},
+    {"transfer", "transfer kernels", "are", "inflatox_amd.background.transfer_functions", "INFLX_TR_ABI", INFLX_TR_ABI_VERSION,
+     {"inflx_tr_init", "inflx_tr_advance_rk4", "inflx_tr_advance_rkf"}},
+    {"modes", "mode-function kernels", "are", "inflatox_amd.background.power_spectra", "INFLX_MD_ABI", INFLX_MD_ABI_VERSION,
+     {"inflx_md_init", "inflx_md_advance_rk4", "inflx_md_advance_rkf"}},
+    {"tensor", "tensor-mode kernels", "are", "inflatox_amd.background.tensor_spectra", "INFLX_TN_ABI", INFLX_TN_ABI_VERSION,
+     {"inflx_tn_init", "inflx_tn_advance_rk4", "inflx_tn_advance_rkf"}},
+    {"deltan", "delta-N kernels", "are", "inflatox_amd.background.delta_N", "INFLX_DN_ABI", INFLX_DN_ABI_VERSION,
+     {"inflx_dn_init", "inflx_dn_reduce", "inflx_dn_end_rk4", "inflx_dn_end_rkf", "inflx_dn_surface_rk4", "inflx_dn_surface_rkf"}},
+};
+
+// Load the companion object `which` beside the core object, unless the handle has it: it must carry the core object's VERSION and
+// MODEL_TAG and this library's value of its layout word.
+int need_companion(inflx_model* m, Companion which) {
+  CompanionSlot& slot = m->companion[which];
+  if (slot.module) return INFLX_OK;
+  const CompanionDesc& d = kCompanions[which];
+  const std::string path = m->path + "." + d.suffix;
   FILE* fh = fopen(path.c_str(), "rb");
   if (!fh)
-    return fail(INFLX_ERR_SYMBOL, "the background kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_background() "
-                "(inflatox_amd.background does on first use)", m->path.c_str(), path.c_str());
+    return fail(INFLX_ERR_SYMBOL, "the %s of %s %s not loaded and no %s exists: build it with CompilationArtifact.ensure_%s() (%s does on first use)", d.label,
+                m->path.c_str(), d.verb, path.c_str(), d.suffix, d.python);
   fclose(fh);
   HIP_TRY(hipSetDevice(m->device));
   hipModule_t module = nullptr;
@@ -2942,68 +2965,134 @@ int need_background(inflx_model* m) {
   uint32_t abi = 0;
   char tag[128] = {0};
   int rc;
-  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_BG_ABI", &abi, sizeof abi, true)) ||
+  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), d.abi_symbol, &abi, sizeof abi, true)) ||
       (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
     return bail(rc);
-  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_BG_ABI_VERSION || m->tag != tag)
-    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another ABI (tag \"%s\", expected \"%s\")",
-                     path.c_str(), m->path.c_str(), tag, m->tag.c_str()));
-  const char* names[2][2] = {{"inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows"}, {"inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows"}};
-  const char* target_names[2] = {"inflx_bg_advance_rk4_target", "inflx_bg_advance_rkf_target"};
-  const char* sampled_names[2] = {"inflx_bg_advance_rk4_sampled", "inflx_bg_advance_rkf_sampled"};
-  hipFunction_t init = nullptr, adv[2][2] = {}, tgt[2] = {}, smp[2] = {}, transpose = nullptr;
-  if (hipModuleGetFunction(&init, module, "inflx_bg_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_bg_init", path.c_str()));
-  if (hipModuleGetFunction(&transpose, module, "inflx_bg_rows_transpose") != hipSuccess)
-    return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_bg_rows_transpose", path.c_str()));
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b)
-      if (hipModuleGetFunction(&adv[a][b], module, names[a][b]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a][b]));
-  for (int a = 0; a < 2; ++a)
-    if (hipModuleGetFunction(&tgt[a], module, target_names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), target_names[a]));
-  for (int a = 0; a < 2; ++a)
-    if (hipModuleGetFunction(&smp[a], module, sampled_names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), sampled_names[a]));
-  m->bg_module = module;
-  m->bg_init = init;
-  m->bg_rows_transpose = transpose;
-  for (int a = 0; a < 2; ++a) m->bg_target[a] = tgt[a];
-  for (int a = 0; a < 2; ++a) m->bg_sampled[a] = smp[a];
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) m->bg_advance[a][b] = adv[a][b];
+  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != d.abi || m->tag != tag)
+    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
+                     "%s %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), d.abi_symbol, abi, (unsigned)d.abi));
+  hipFunction_t fn[kCompanionKernels] = {};
+  for (int k = 0; d.kernels[k]; ++k)
+    if (hipModuleGetFunction(&fn[k], module, d.kernels[k]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), d.kernels[k]));
+  slot.module = module;
+  std::copy(fn, fn + kCompanionKernels, slot.fn);
   note_sf_word(m, module);
   return INFLX_OK;
 }
 
-// device buffers of one call, released on every way out
-struct BgBuffers {
-  double *p = nullptr, *init = nullptr, *carry = nullptr, *rows = nullptr, *target = nullptr, *samples = nullptr;
-  double *out_y = nullptr, *out_t = nullptr;  // a pass's whole result in the caller's layout (inflx_solve_eom's host result)
-  uint32_t* running = nullptr;
-  ~BgBuffers() {
-    for (double* d : {p, init, carry, rows, target, samples, out_y, out_t})
-      if (d) (void)hipFree(d);
-    if (running) (void)hipFree(running);
-  }
-};
-
-
-// the argument checks inflx_solve_eom and inflx_solve_eom_device share, in inflx_solve_eom's order
-int check_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, size_t B, size_t rows, size_t substeps, int method, double max_err, double dt,
-                    unsigned flags, unsigned known_flags, const int8_t* status) {
+// The checks of the arguments every integrating entry point has, in the order all of them make them: handle, fields, parameter rows,
+// method and flags; then `between`, the checks of the family's own arguments that stand there (rows and substeps, the stencil);
+// then max_steps, max_err, dt and status.  `phrase` and `noun` are the family's words: "the background solver requires", "trajectory".
+template <class Between>
+int check_integrator_args(const inflx_model* m, const char* phrase, const char* noun, const double* p, size_t P, size_t n_p, size_t B, int method, unsigned flags,
+                          unsigned known_flags, Between between, size_t max_steps, double max_err, double dt, const void* status) {
   if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the background solver requires a 2-field model (model has %u fields)", m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "%s a 2-field model (model has %u fields)", phrase, m->dim);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u parameters (got %zu)", m->name.c_str(), m->n_par, n_p);
   if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
-  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
+  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per %s (%zu)", P, noun, B);
   if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
   if (flags & ~known_flags) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
-  if (rows < 1) return fail(INFLX_ERR_ARG, "rows must be at least 1 (got %zu)", rows);
-  if (substeps < 1 || substeps > 0xffffffffu) return fail(INFLX_ERR_ARG, "substeps must be in [1, 2^32) (got %zu)", substeps);
-  if ((uint64_t)(rows - 1) > (UINT64_C(1) << 62) / substeps) return fail(INFLX_ERR_ARG, "rows x substeps exceeds 2^62 accepted steps");
+  if (const int rc = between()) return rc;
+  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
   if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
   if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
   if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
   return INFLX_OK;
 }
+// ... of a family with nothing in between
+int check_integrator_args(const inflx_model* m, const char* phrase, const char* noun, const double* p, size_t P, size_t n_p, size_t B, int method, unsigned flags,
+                          unsigned known_flags, size_t max_steps, double max_err, double dt, const void* status) {
+  return check_integrator_args(m, phrase, noun, p, P, n_p, B, method, flags, known_flags, [] { return (int)INFLX_OK; }, max_steps, max_err, dt, status);
+}
+
+// the list of S samples all lanes of a call share: finite, >= 0, strictly increasing
+int check_samples(const double* samples, size_t S) {
+  if (S < 1 || (uint64_t)S > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of samples must be in [1, 2^32) (got %zu)", S);
+  if (!samples) return fail(INFLX_ERR_ARG, "sample array is NULL");
+  for (size_t k = 0; k < S; ++k) {
+    if (!std::isfinite(samples[k]) || samples[k] < 0.0) return fail(INFLX_ERR_ARG, "sample %zu is not a finite number >= 0", k);
+    if (k && !(samples[k] > samples[k - 1])) return fail(INFLX_ERR_ARG, "samples must be strictly increasing (sample %zu is not above sample %zu)", k, k - 1);
+  }
+  return INFLX_OK;
+}
+
+// The device buffers of one call: typed arrays, all of them released on every way out.
+class DeviceBuffers {
+ public:
+  DeviceBuffers() = default;
+  DeviceBuffers(const DeviceBuffers&) = delete;
+  DeviceBuffers& operator=(const DeviceBuffers&) = delete;
+  ~DeviceBuffers() {
+    for (void* d : owned_) (void)hipFree(d);  // (a null, left by an allocation that failed, is freed as nothing)
+  }
+  // *out: `count` elements of T
+  template <class T>
+  int array(T** out, size_t count) {
+    owned_.push_back(nullptr);
+    HIP_TRY(hipMalloc(&owned_.back(), count * sizeof(T)));
+    *out = static_cast<T*>(owned_.back());
+    return INFLX_OK;
+  }
+  // *out: the P parameter rows of n_p doubles, their upload enqueued on `s`
+  int params(double** out, const double* p, size_t P, size_t n_p, hipStream_t s) {
+    if (const int rc = array(out, std::max<size_t>(1, P * n_p))) return rc;
+    if (P * n_p) HIP_TRY(hipMemcpyAsync(*out, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
+    return INFLX_OK;
+  }
+
+ private:
+  std::vector<void*> owned_;
+};
+
+// a.step_begin = step, where the argument block has such a field (InflxBgArgs: the *_target and *_sampled kernels)
+template <class Args>
+auto set_step_begin(Args& a, uint64_t step, int) -> decltype(void(a.step_begin)) {
+  a.step_begin = step;
+}
+template <class Args>
+void set_step_begin(Args&, uint64_t, long) {}
+
+// Launches of `fn` on the argument block `a`, of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps each, until max_steps run out or a
+// launch leaves no lane running (the word a.running, cleared before every launch and read back after it).
+template <class Args>
+int advance_until_done(hipFunction_t fn, Args& a, unsigned grid, unsigned threads, size_t max_steps, hipStream_t s) {
+  void* params[] = {&a};
+  for (uint64_t step = 0; step < (uint64_t)max_steps;) {
+    const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
+    set_step_begin(a, step, 0);
+    a.steps = (uint32_t)k;
+    uint32_t running = 0;
+    HIP_TRY(hipMemsetAsync(a.running, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, threads, 1, 1, 0, s, params, nullptr));
+    HIP_TRY(hipMemcpyAsync(&running, a.running, sizeof running, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    step += k;
+    if (running == 0) break;
+  }
+  return INFLX_OK;
+}
+
+}  // namespace
+
+// ---- background trajectories (inflx_solve_eom) ------------------------------------------------------------------------------
+namespace {
+
+// the kernels' argument block and the carry planes: csrc/inflx_background_abi.h
+
+// the argument checks inflx_solve_eom and inflx_solve_eom_device share, in inflx_solve_eom's order
+int check_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, size_t B, size_t rows, size_t substeps, int method, double max_err, double dt,
+                    unsigned flags, unsigned known_flags, const int8_t* status) {
+  auto rows_and_substeps = [&]() -> int {
+    if (rows < 1) return fail(INFLX_ERR_ARG, "rows must be at least 1 (got %zu)", rows);
+    if (substeps < 1 || substeps > 0xffffffffu) return fail(INFLX_ERR_ARG, "substeps must be in [1, 2^32) (got %zu)", substeps);
+    if ((uint64_t)(rows - 1) > (UINT64_C(1) << 62) / substeps) return fail(INFLX_ERR_ARG, "rows x substeps exceeds 2^62 accepted steps");
+    return INFLX_OK;
+  };
+  // (max_steps = 0: the steps of these calls are rows x substeps, checked above)
+  return check_integrator_args(m, "the background solver requires", "trajectory", p, P, n_p, B, method, flags, known_flags, rows_and_substeps, 0, max_err, dt, status);
+}
+
 
 // The passes of inflx_solve_eom and inflx_solve_eom_device on stream `s`, arguments checked and the background object loaded.
 // `device_result`: `states` and `t` are the caller's device arrays and every window of rows is transposed straight into them.
@@ -3022,26 +3111,26 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
   size_t cap_rows = 0;  // rows the device row buffer holds
   if (store) cap_rows = std::max<size_t>(2, std::min(rows, kBgRowBytes / (7 * sizeof(double) * nc_max)));
   const uint64_t total_steps = (uint64_t)(rows - 1) * substeps;  // accepted-step indices of the call (checked against overflow above)
-  BgBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
-  if (store) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.rows), cap_rows * 7 * nc_max * sizeof(double)));
-  if (staged && states) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out_y), nc_max * rows * 6 * sizeof(double)));
-  if (staged && t) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out_t), nc_max * rows * sizeof(double)));
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_init = nullptr, *d_carry = nullptr, *d_rows = nullptr;
+  double *d_out_y = nullptr, *d_out_t = nullptr;  // a pass's whole result in the caller's layout (inflx_solve_eom's host result)
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_carry, nc_max * INFLX_BG_CARRY_PLANES))) return rc;
+  if (store && (rc = dev.array(&d_rows, cap_rows * 7 * nc_max))) return rc;
+  if (staged && states && (rc = dev.array(&d_out_y, nc_max * rows * 6))) return rc;
+  if (staged && t && (rc = dev.array(&d_out_t, nc_max * rows))) return rc;
   std::vector<double> host_rows(store && !transposed ? cap_rows * 7 * nc_max : 0), host_carry(nc_max * INFLX_BG_CARRY_ROW_PLANES);
-  hipFunction_t advance = m->bg_advance[method == INFLX_EOM_RKF ? 1 : 0][store ? 1 : 0];
+  const CompanionSlot& bg = m->companion[kObjBackground];
+  hipFunction_t advance = bg.fn[kBgAdvance + 2 * (method == INFLX_EOM_RKF ? 1 : 0) + (store ? 1 : 0)];
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxBgArgs a;
     memset(&a, 0, sizeof a);
-    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
     a.p_stride = P == 1 ? 0 : n_p;
-    a.init = buf.init;
-    a.carry = buf.carry;
-    a.rows = store ? buf.rows : nullptr;
+    a.init = d_init;
+    a.carry = d_carry;
+    a.rows = store ? d_rows : nullptr;
     a.n = n;
     a.substeps = (uint32_t)substeps;
     a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
@@ -3049,8 +3138,8 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
     a.fixed_dt = dt;
     void* params[] = {&a};
     const unsigned grid = (unsigned)((n + 255) / 256);
-    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipModuleLaunchKernel(m->bg_init, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipModuleLaunchKernel(bg.fn[kBgInit], grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
     // the device buffer holds rows [row_base, rows_done): rows_done = 1 + the rows completed by the steps taken so far
     uint64_t row_base = 0, rows_done = 1, step = 0;
     // the window [row_base, rows_done) leaves the row buffer: through the transpose kernel, which the stream orders before the next
@@ -3061,9 +3150,9 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
       if (transposed) {
         InflxBgRowsArgs ta;
         memset(&ta, 0, sizeof ta);
-        ta.rows = buf.rows;
-        ta.out_y = staged ? buf.out_y : states;
-        ta.out_t = staged ? buf.out_t : t;
+        ta.rows = d_rows;
+        ta.out_y = staged ? d_out_y : states;
+        ta.out_t = staged ? d_out_t : t;
         ta.n = n;
         ta.lane_off = staged ? 0 : c0;
         ta.rows_total = rows;
@@ -3071,11 +3160,11 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
         ta.filled = filled;
         void* tparams[] = {&ta};
         // (at most 2^28 / 56 row cells in a window: the grid is far below 2^31 workgroups)
-        HIP_TRY(hipModuleLaunchKernel(m->bg_rows_transpose, (unsigned)inflx_bg_rows_blocks(n, filled), 1, 1, INFLX_BG_ROWS_THREADS, 1, 1, 0, s, tparams, nullptr));
+        HIP_TRY(hipModuleLaunchKernel(bg.fn[kBgRowsTranspose], (unsigned)inflx_bg_rows_blocks(n, filled), 1, 1, INFLX_BG_ROWS_THREADS, 1, 1, 0, s, tparams, nullptr));
         row_base = rows_done;
         return INFLX_OK;
       }
-      HIP_TRY(hipMemcpyAsync(host_rows.data(), buf.rows, filled * 7 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(host_rows.data(), d_rows, filled * 7 * n * sizeof(double), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       for (size_t r = 0; r < filled; ++r) {
         const double* plane = host_rows.data() + r * 7 * n;
@@ -3111,9 +3200,9 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
       }
     }
     if (store && (rc = drain())) return rc;  // (rows == 1: the initial state only)
-    if (staged && states) HIP_TRY(hipMemcpyAsync(states + c0 * rows * 6, buf.out_y, n * rows * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (staged && t) HIP_TRY(hipMemcpyAsync(t + c0 * rows, buf.out_t, n * rows * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_ROW_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (staged && states) HIP_TRY(hipMemcpyAsync(states + c0 * rows * 6, d_out_y, n * rows * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (staged && t) HIP_TRY(hipMemcpyAsync(t + c0 * rows, d_out_t, n * rows * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry, n * INFLX_BG_CARRY_ROW_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
@@ -3142,7 +3231,7 @@ int inflx_solve_eom(inflx_model* m, const double* p, size_t P, size_t n_p, const
   if (B == 0) return INFLX_OK;
   if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
   HIP_TRY(hipSetDevice(m->device));
-  if ((rc = need_background(m))) return rc;
+  if ((rc = need_companion(m, kObjBackground))) return rc;
   return solve_eom_passes(m, m->stream, p, P, n_p, init, B, rows, substeps, method, max_err, dt, flags, states, t, /*device_result=*/false, efolds, status, last_row);
 }
 
@@ -3161,7 +3250,7 @@ int inflx_solve_eom_device(inflx_model* m, const double* p, size_t P, size_t n_p
   if (B == 0) return INFLX_OK;
   if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
   HIP_TRY(hipSetDevice(m->device));
-  if ((rc = need_background(m))) return rc;
+  if ((rc = need_companion(m, kObjBackground))) return rc;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
   return solve_eom_passes(m, s, p, P, n_p, init, B, rows, substeps, method, max_err, dt, flags, d_states, d_t, /*device_result=*/true, efolds, status, last_row);
 }
@@ -3170,71 +3259,49 @@ int inflx_solve_eom_to_efolds(inflx_model* m, const double* p, size_t P, size_t 
                               int method, double max_err, double dt, unsigned flags, double* states, double* t, double* eps_h, double* efolds,
                               int8_t* status) {
   INFLX_SERIALISE(m);
-  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the background solver requires a 2-field model (model has %u fields)", m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
-  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
-  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
-  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
-  if (flags & ~(unsigned)INFLX_EOM_STOP_AT_END) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
-  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
-  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
-  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  int rc = check_integrator_args(m, "the background solver requires", "trajectory", p, P, n_p, B, method, flags, INFLX_EOM_STOP_AT_END, max_steps, max_err, dt, status);
+  if (rc) return rc;
   if (B == 0) return INFLX_OK;
   if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
   if (!target) return fail(INFLX_ERR_ARG, "target array is NULL");
   for (size_t l = 0; l < B; ++l)
     if (std::isnan(target[l])) return fail(INFLX_ERR_ARG, "target %zu is NaN", l);
   HIP_TRY(hipSetDevice(m->device));
-  int rc = need_background(m);
-  if (rc) return rc;
+  if ((rc = need_companion(m, kObjBackground))) return rc;
   hipStream_t s = m->stream;
   const size_t nc_max = std::min(B, kBgMaxLanes);
-  BgBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.target), nc_max * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_init = nullptr, *d_target = nullptr, *d_carry = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_target, nc_max)) ||
+      (rc = dev.array(&d_carry, nc_max * INFLX_BG_CARRY_PLANES)) || (rc = dev.array(&d_running, 1)))
+    return rc;
   std::vector<double> host_carry(nc_max * INFLX_BG_CARRY_PLANES);
-  hipFunction_t advance = m->bg_target[method == INFLX_EOM_RKF ? 1 : 0];
+  const CompanionSlot& bg = m->companion[kObjBackground];
+  hipFunction_t advance = bg.fn[kBgTarget + (method == INFLX_EOM_RKF ? 1 : 0)];
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxBgArgs a;
     memset(&a, 0, sizeof a);
-    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
     a.p_stride = P == 1 ? 0 : n_p;
-    a.init = buf.init;
-    a.carry = buf.carry;
+    a.init = d_init;
+    a.carry = d_carry;
     a.n = n;
     a.substeps = 1;
     a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
     a.max_err = max_err;
     a.fixed_dt = dt;
-    a.target = buf.target;
-    a.running = buf.running;
+    a.target = d_target;
+    a.running = d_running;
     void* params[] = {&a};
     const unsigned grid = (unsigned)((n + 255) / 256);
-    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(buf.target, target + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipModuleLaunchKernel(m->bg_init, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
-    // launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
-    for (uint64_t step = 0; step < (uint64_t)max_steps;) {
-      const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
-      a.step_begin = step;
-      a.steps = (uint32_t)k;
-      uint32_t running = 0;
-      HIP_TRY(hipMemsetAsync(buf.running, 0, sizeof(uint32_t), s));
-      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
-      HIP_TRY(hipMemcpyAsync(&running, buf.running, sizeof running, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      step += k;
-      if (running == 0) break;
-    }
-    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_target, target + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipModuleLaunchKernel(bg.fn[kBgInit], grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(advance, a, grid, 256, max_steps, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry, n * INFLX_BG_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
@@ -3253,87 +3320,57 @@ int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_
                             size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status,
                             uint32_t* n_stored) {
   INFLX_SERIALISE(m);
-  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the background solver requires a 2-field model (model has %u fields)", m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
-  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
-  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
-  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
-  if (flags & ~(unsigned)(INFLX_EOM_STOP_AT_END | INFLX_EOM_SAMPLE_T)) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
-  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
-  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
-  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
-  if (S < 1 || (uint64_t)S > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of samples must be in [1, 2^32) (got %zu)", S);
-  if (!samples) return fail(INFLX_ERR_ARG, "sample array is NULL");
-  for (size_t k = 0; k < S; ++k) {
-    if (!std::isfinite(samples[k]) || samples[k] < 0.0) return fail(INFLX_ERR_ARG, "sample %zu is not a finite number >= 0", k);
-    if (k && !(samples[k] > samples[k - 1])) return fail(INFLX_ERR_ARG, "samples must be strictly increasing (sample %zu is not above sample %zu)", k, k - 1);
-  }
+  int rc = check_integrator_args(m, "the background solver requires", "trajectory", p, P, n_p, B, method, flags, INFLX_EOM_STOP_AT_END | INFLX_EOM_SAMPLE_T, max_steps, max_err,
+                                 dt, status);
+  if (rc || (rc = check_samples(samples, S))) return rc;
   if (B == 0) return INFLX_OK;
   if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
   if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
   HIP_TRY(hipSetDevice(m->device));
-  int rc = need_background(m);
-  if (rc) return rc;
+  if ((rc = need_companion(m, kObjBackground))) return rc;
   hipStream_t s = m->stream;
-  // lanes reach a sample in different launches, so the device buffer holds all S samples of a pass's lanes: the lanes of a pass are
-  // bounded by the row buffer's bytes (whole workgroups where more than one fits)
-  size_t nc_max = std::max<size_t>(1, kBgRowBytes / (8 * sizeof(double) * S));
-  if (nc_max > 256) nc_max -= nc_max % 256;
-  nc_max = std::min({B, kBgMaxLanes, nc_max});
+  // lanes reach a sample in different launches, so the device buffer holds all S samples of a pass's lanes
   const size_t plane_bytes = S * 8 * sizeof(double);  // (of one lane)
-  BgBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.samples), S * sizeof(double)));
-  HIP_TRY(hipMemcpyAsync(buf.samples, samples, S * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_BG_CARRY_PLANES * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.rows), nc_max * plane_bytes));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  const size_t nc_max = inflx_bg_lanes_per_pass(B, plane_bytes, 256);
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_samples = nullptr, *d_init = nullptr, *d_carry = nullptr, *d_rows = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_samples, S))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_samples, samples, S * sizeof(double), hipMemcpyHostToDevice, s));
+  if ((rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_carry, nc_max * INFLX_BG_CARRY_PLANES)) || (rc = dev.array(&d_rows, nc_max * S * 8)) ||
+      (rc = dev.array(&d_running, 1)))
+    return rc;
   std::vector<double> host_carry(nc_max * INFLX_BG_CARRY_ROW_PLANES);
-  hipFunction_t advance = m->bg_sampled[method == INFLX_EOM_RKF ? 1 : 0];
+  const CompanionSlot& bg = m->companion[kObjBackground];
+  hipFunction_t advance = bg.fn[kBgSampled + (method == INFLX_EOM_RKF ? 1 : 0)];
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxBgArgs a;
     memset(&a, 0, sizeof a);
-    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
     a.p_stride = P == 1 ? 0 : n_p;
-    a.init = buf.init;
-    a.carry = buf.carry;
-    a.rows = buf.rows;
+    a.init = d_init;
+    a.carry = d_carry;
+    a.rows = d_rows;
     a.n = n;
     a.substeps = 1;
     a.flags = ((flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u) | ((flags & INFLX_EOM_SAMPLE_T) ? 2u : 0u);
     a.n_samples = (uint32_t)S;
     a.max_err = max_err;
     a.fixed_dt = dt;
-    a.running = buf.running;
-    a.samples = buf.samples;
+    a.running = d_running;
+    a.samples = d_samples;
     void* params[] = {&a};
     const unsigned grid = (unsigned)((n + 255) / 256);
-    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
     // every byte 0xff: each double is a NaN, which a sample that its lane never reaches keeps
-    HIP_TRY(hipMemsetAsync(buf.rows, 0xff, n * plane_bytes, s));
-    HIP_TRY(hipModuleLaunchKernel(m->bg_init, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
-    // launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
-    for (uint64_t step = 0; step < (uint64_t)max_steps;) {
-      const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
-      a.step_begin = step;
-      a.steps = (uint32_t)k;
-      uint32_t running = 0;
-      HIP_TRY(hipMemsetAsync(buf.running, 0, sizeof(uint32_t), s));
-      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
-      HIP_TRY(hipMemcpyAsync(&running, buf.running, sizeof running, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      step += k;
-      if (running == 0) break;
-    }
+    HIP_TRY(hipMemsetAsync(d_rows, 0xff, n * plane_bytes, s));
+    HIP_TRY(hipModuleLaunchKernel(bg.fn[kBgInit], grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(advance, a, grid, 256, max_steps, s))) return rc;
     // the planes as they are: plane (sample, component) of this pass's lanes is n doubles, B doubles apart in `out`
-    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.rows, n * sizeof(double), n * sizeof(double), 8 * S, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry, n * INFLX_BG_CARRY_ROW_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), d_rows, n * sizeof(double), n * sizeof(double), 8 * S, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry, n * INFLX_BG_CARRY_ROW_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
@@ -3350,68 +3387,24 @@ int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_
 // ---- pointwise passes over states: trajectory kinematics (inflx_kinematics) and entropic masses (inflx_masses) ----------------
 namespace {
 
-static_assert(kAbiMajor == INFLX_KIN_DEFAULT_ABI_MAJOR, "a kinematics object reports the core object's ABI major: change both together");
-static_assert(kAbiMajor == INFLX_MASS_DEFAULT_ABI_MAJOR, "a masses object reports the core object's ABI major: change both together");
 static_assert(sizeof(InflxMassArgs) == sizeof(InflxKinArgs), "InflxMassArgs has the fields of InflxKinArgs");
 
-// One such pass: a kernel of one lane per state in a code object of its own, `<artefact>.<what>`, which
-// CompilationArtifact.ensure_<what>() builds and inflatox_amd.background.<what> calls.
+// One such pass: the kernel kStates of its companion object, one lane per state; inflatox_amd.background.<what> calls it.
 struct StatePass {
+  Companion object;
   const char* what;
-  const char* abi_symbol;  // the object's layout word
-  uint32_t abi;            // ... and this library's value of it
-  const char* kernel;
   unsigned threads;
   size_t planes;  // quantities per state
-  hipModule_t inflx_model::*module;
-  hipFunction_t inflx_model::*states;
 };
-const StatePass kKinematics = {"kinematics", "INFLX_KIN_ABI", INFLX_KIN_ABI_VERSION, "inflx_kin_states", INFLX_KIN_THREADS, INFLX_KIN_PLANES, &inflx_model::kin_module, &inflx_model::kin_states};
-const StatePass kMasses = {"masses", "INFLX_MASS_ABI", INFLX_MASS_ABI_VERSION, "inflx_mass_states", INFLX_MASS_THREADS, INFLX_MASS_PLANES, &inflx_model::mass_module, &inflx_model::mass_states};
-
-// Load `<artefact>.<what>` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
-int need_state_pass(inflx_model* m, const StatePass& pass) {
-  if (m->*pass.module) return INFLX_OK;
-  const std::string path = m->path + "." + pass.what;
-  FILE* fh = fopen(path.c_str(), "rb");
-  if (!fh)
-    return fail(INFLX_ERR_SYMBOL, "the %s kernel of %s is not loaded and no %s exists: build it with CompilationArtifact.ensure_%s() "
-                "(inflatox_amd.background.%s does on first use)", pass.what, m->path.c_str(), path.c_str(), pass.what, pass.what);
-  fclose(fh);
-  HIP_TRY(hipSetDevice(m->device));
-  hipModule_t module = nullptr;
-  hipError_t e = hipModuleLoad(&module, path.c_str());
-  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
-  auto bail = [&](int code) {
-    const std::string first = g_last_error;
-    (void)hipModuleUnload(module);
-    g_last_error = first;
-    return code;
-  };
-  uint16_t version[3] = {};
-  uint32_t abi = 0;
-  char tag[128] = {0};
-  int rc;
-  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), pass.abi_symbol, &abi, sizeof abi, true)) ||
-      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
-    return bail(rc);
-  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != pass.abi || m->tag != tag)
-    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
-                     "%s %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), pass.abi_symbol, abi, (unsigned)pass.abi));
-  hipFunction_t states = nullptr;
-  if (hipModuleGetFunction(&states, module, pass.kernel) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), pass.kernel));
-  m->*pass.module = module;
-  m->*pass.states = states;
-  note_sf_word(m, module);
-  return INFLX_OK;
-}
+const StatePass kKinematics = {kObjKinematics, "kinematics", INFLX_KIN_THREADS, INFLX_KIN_PLANES};
+const StatePass kMasses = {kObjMasses, "masses", INFLX_MASS_THREADS, INFLX_MASS_PLANES};
 
 // the argument checks the host and the device form of a pass share; *span: the doubles of `states` the call reads
 int check_state_pass(inflx_model* m, const StatePass& pass, const double* p, size_t P, size_t n_p, const void* states, size_t n, size_t ld, size_t traj_len, const void* out,
                      size_t* span) {
   if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
   if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the %s require a 2-field model (model has %u fields)", pass.what, m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
+  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u parameters (got %zu)", m->name.c_str(), m->n_par, n_p);
   if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
   if (ld < 5) return fail(INFLX_ERR_SHAPE, "a state has five components: ld must be at least 5 (got %zu)", ld);
   if (traj_len < 1) return fail(INFLX_ERR_ARG, "traj_len must be at least 1");
@@ -3426,14 +3419,6 @@ int check_state_pass(inflx_model* m, const StatePass& pass, const double* p, siz
   *span = doubles;
   return INFLX_OK;
 }
-
-struct KinBuffers {
-  double *p = nullptr, *y = nullptr, *out = nullptr;
-  ~KinBuffers() {
-    for (double* d : {p, y, out})
-      if (d) (void)hipFree(d);
-  }
-};
 
 // one launch: states [first, first + n) of the call, at d_y, into the planes d_out [pass.planes][n].  Args: InflxKinArgs or InflxMassArgs
 template <class Args>
@@ -3450,7 +3435,7 @@ int launch_state_pass(inflx_model* m, const StatePass& pass, hipStream_t s, cons
   a.p_stride = p_stride;
   a.first = first;
   void* params[] = {&a};
-  HIP_TRY(hipModuleLaunchKernel(m->*pass.states, (unsigned)((n + pass.threads - 1) / pass.threads), 1, 1, pass.threads, 1, 1, 0, s, params, nullptr));
+  HIP_TRY(hipModuleLaunchKernel(m->companion[pass.object].fn[kStates], (unsigned)((n + pass.threads - 1) / pass.threads), 1, 1, pass.threads, 1, 1, 0, s, params, nullptr));
   return INFLX_OK;
 }
 
@@ -3462,20 +3447,18 @@ int state_pass_host(inflx_model* m, const StatePass& pass, const double* p, size
   if (rc) return rc;
   if (n == 0) return INFLX_OK;
   HIP_TRY(hipSetDevice(m->device));
-  if ((rc = need_state_pass(m, pass))) return rc;
+  if ((rc = need_companion(m, pass.object))) return rc;
   hipStream_t s = m->stream;
   const size_t chunk = std::min(n, kBgMaxLanes);  // the lane bound of a pass of the solver
-  KinBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.y), ((chunk - 1) * ld + 5) * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), chunk * pass.planes * sizeof(double)));
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_y = nullptr, *d_out = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_y, (chunk - 1) * ld + 5)) || (rc = dev.array(&d_out, chunk * pass.planes))) return rc;
   for (size_t c0 = 0; c0 < n; c0 += chunk) {
     const size_t nc = std::min(chunk, n - c0);
-    HIP_TRY(hipMemcpyAsync(buf.y, states + c0 * ld, ((nc - 1) * ld + 5) * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = launch_state_pass<Args>(m, pass, s, buf.y, buf.p, P == 1 ? 0 : n_p, buf.out, nc, ld, traj_len, c0))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_y, states + c0 * ld, ((nc - 1) * ld + 5) * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = launch_state_pass<Args>(m, pass, s, d_y, d_p, P == 1 ? 0 : n_p, d_out, nc, ld, traj_len, c0))) return rc;
     // the plane segments of this chunk: nc doubles each, n doubles apart in `out`
-    HIP_TRY(hipMemcpy2DAsync(out + c0, n * sizeof(double), buf.out, nc * sizeof(double), nc * sizeof(double), pass.planes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(out + c0, n * sizeof(double), d_out, nc * sizeof(double), nc * sizeof(double), pass.planes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   return sf_verdict(m);
@@ -3494,12 +3477,12 @@ int state_pass_device(inflx_model* m, const StatePass& pass, const double* p, si
   if ((n + pass.threads - 1) / pass.threads > 0x7fffffffu) return fail(INFLX_ERR_SHAPE, "%zu states exceed one launch (2^31 - 1 workgroups of %u)", n, pass.threads);
   if (n == 0) return INFLX_OK;
   HIP_TRY(hipSetDevice(m->device));
-  if ((rc = need_state_pass(m, pass))) return rc;
+  if ((rc = need_companion(m, pass.object))) return rc;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->stream;
-  KinBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  if ((rc = launch_state_pass<Args>(m, pass, s, static_cast<const double*>(d_states), buf.p, P == 1 ? 0 : n_p, static_cast<double*>(d_out), n, ld, traj_len, 0))) return rc;
+  DeviceBuffers dev;
+  double* d_p = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s))) return rc;
+  if ((rc = launch_state_pass<Args>(m, pass, s, static_cast<const double*>(d_states), d_p, P == 1 ? 0 : n_p, static_cast<double*>(d_out), n, ld, traj_len, 0))) return rc;
   HIP_TRY(hipStreamSynchronize(s));  // (the parameter rows live until the kernel has read them)
   return sf_verdict(m);
 }
@@ -3533,87 +3516,14 @@ int inflx_masses_device(inflx_model* m, const double* p, size_t P, size_t n_p, c
 }  // extern "C"
 
 // ---- super-horizon transfer functions (inflx_transfer_functions) ------------------------------------------------------------------
-namespace {
-
-static_assert(kAbiMajor == INFLX_TR_DEFAULT_ABI_MAJOR, "a transfer object reports the core object's ABI major: change both together");
-
-// Load `<artefact>.transfer` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
-int need_transfer(inflx_model* m) {
-  if (m->tr_module) return INFLX_OK;
-  const std::string path = m->path + ".transfer";
-  FILE* fh = fopen(path.c_str(), "rb");
-  if (!fh)
-    return fail(INFLX_ERR_SYMBOL, "the transfer kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_transfer() "
-                "(inflatox_amd.background.transfer_functions does on first use)", m->path.c_str(), path.c_str());
-  fclose(fh);
-  HIP_TRY(hipSetDevice(m->device));
-  hipModule_t module = nullptr;
-  hipError_t e = hipModuleLoad(&module, path.c_str());
-  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
-  auto bail = [&](int code) {
-    const std::string first = g_last_error;
-    (void)hipModuleUnload(module);
-    g_last_error = first;
-    return code;
-  };
-  uint16_t version[3] = {};
-  uint32_t abi = 0;
-  char tag[128] = {0};
-  int rc;
-  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_TR_ABI", &abi, sizeof abi, true)) ||
-      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
-    return bail(rc);
-  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_TR_ABI_VERSION || m->tag != tag)
-    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
-                     "INFLX_TR_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_TR_ABI_VERSION));
-  const char* names[2] = {"inflx_tr_advance_rk4", "inflx_tr_advance_rkf"};
-  hipFunction_t init = nullptr, adv[2] = {};
-  if (hipModuleGetFunction(&init, module, "inflx_tr_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_tr_init", path.c_str()));
-  for (int a = 0; a < 2; ++a)
-    if (hipModuleGetFunction(&adv[a], module, names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a]));
-  m->tr_module = module;
-  m->tr_init = init;
-  for (int a = 0; a < 2; ++a) m->tr_advance[a] = adv[a];
-  note_sf_word(m, module);
-  return INFLX_OK;
-}
-
-// device buffers of one call, released on every way out
-struct TrBuffers {
-  double *p = nullptr, *init = nullptr, *dq = nullptr, *carry = nullptr, *out = nullptr, *samples = nullptr;
-  uint32_t* running = nullptr;
-  ~TrBuffers() {
-    for (double* d : {p, init, dq, carry, out, samples})
-      if (d) (void)hipFree(d);
-    if (running) (void)hipFree(running);
-  }
-};
-
-}  // namespace
-
 extern "C" {
 
 int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* dq_dn, const double* samples,
                              size_t S, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* ends, double* efolds,
                              int8_t* status, uint32_t* n_stored) {
   INFLX_SERIALISE(m);
-  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the transfer functions require a 2-field model (model has %u fields)", m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u paramters (got %zu)", m->name.c_str(), m->n_par, n_p);
-  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
-  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per trajectory (%zu)", P, B);
-  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
-  if (flags & ~(unsigned)INFLX_EOM_STOP_AT_END) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
-  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
-  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
-  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
-  if (S < 1 || (uint64_t)S > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of samples must be in [1, 2^32) (got %zu)", S);
-  if (!samples) return fail(INFLX_ERR_ARG, "sample array is NULL");
-  for (size_t k = 0; k < S; ++k) {
-    if (!std::isfinite(samples[k]) || samples[k] < 0.0) return fail(INFLX_ERR_ARG, "sample %zu is not a finite number >= 0", k);
-    if (k && !(samples[k] > samples[k - 1])) return fail(INFLX_ERR_ARG, "samples must be strictly increasing (sample %zu is not above sample %zu)", k, k - 1);
-  }
+  int rc = check_integrator_args(m, "the transfer functions require", "trajectory", p, P, n_p, B, method, flags, INFLX_EOM_STOP_AT_END, max_steps, max_err, dt, status);
+  if (rc || (rc = check_samples(samples, S))) return rc;
   if (dq_dn)
     for (size_t l = 0; l < B; ++l)
       if (!std::isfinite(dq_dn[l])) return fail(INFLX_ERR_ARG, "dq_dn %zu is not finite", l);
@@ -3621,41 +3531,37 @@ int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n
   if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
   if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
   HIP_TRY(hipSetDevice(m->device));
-  int rc = need_transfer(m);
-  if (rc) return rc;
+  if ((rc = need_companion(m, kObjTransfer))) return rc;
   hipStream_t s = m->stream;
-  // lanes reach a sample in different launches, so the device buffer holds all S samples of a pass's lanes: the lanes of a pass are
-  // bounded by the row buffer's bytes (whole workgroups where more than one fits), as in inflx_solve_eom_sampled
-  size_t nc_max = std::max<size_t>(1, kBgRowBytes / (INFLX_TR_OUT_PLANES * sizeof(double) * S));
-  if (nc_max > INFLX_TR_THREADS) nc_max -= nc_max % INFLX_TR_THREADS;
-  nc_max = std::min({B, kBgMaxLanes, nc_max});
+  // lanes reach a sample in different launches, so the device buffer holds all S samples of a pass's lanes, as in
+  // inflx_solve_eom_sampled
   const size_t plane_bytes = S * INFLX_TR_OUT_PLANES * sizeof(double);  // (of one lane)
+  const size_t nc_max = inflx_bg_lanes_per_pass(B, plane_bytes, INFLX_TR_THREADS);
   constexpr size_t kBack = INFLX_TR_CARRY_HOST_PLANES - INFLX_TR_CARRY_NEND;  // the carry planes read back: NEND, STATUS, CURSOR, END_SS, END_RS
-  TrBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.samples), S * sizeof(double)));
-  HIP_TRY(hipMemcpyAsync(buf.samples, samples, S * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
-  if (dq_dn) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.dq), nc_max * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * INFLX_TR_CARRY_PLANES * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), nc_max * plane_bytes));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_samples = nullptr, *d_init = nullptr, *d_dq = nullptr, *d_carry = nullptr, *d_out = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_samples, S))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_samples, samples, S * sizeof(double), hipMemcpyHostToDevice, s));
+  if ((rc = dev.array(&d_init, nc_max * 4)) || (dq_dn && (rc = dev.array(&d_dq, nc_max))) || (rc = dev.array(&d_carry, nc_max * INFLX_TR_CARRY_PLANES)) ||
+      (rc = dev.array(&d_out, nc_max * S * INFLX_TR_OUT_PLANES)) || (rc = dev.array(&d_running, 1)))
+    return rc;
   std::vector<double> host_carry(nc_max * kBack);
-  hipFunction_t advance = m->tr_advance[method == INFLX_EOM_RKF ? 1 : 0];
+  const CompanionSlot& tr = m->companion[kObjTransfer];
+  hipFunction_t advance = tr.fn[kLaneAdvance + (method == INFLX_EOM_RKF ? 1 : 0)];
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxTrArgs a;
     memset(&a, 0, sizeof a);
-    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
     a.p_stride = P == 1 ? 0 : n_p;
-    a.init = buf.init;
-    a.dq_dn = buf.dq;
-    a.carry = buf.carry;
-    a.out = buf.out;
-    a.samples = buf.samples;
-    a.running = buf.running;
+    a.init = d_init;
+    a.dq_dn = d_dq;
+    a.carry = d_carry;
+    a.out = d_out;
+    a.samples = d_samples;
+    a.running = d_running;
     a.n = n;
     a.n_samples = (uint32_t)S;
     a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
@@ -3663,26 +3569,15 @@ int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n
     a.fixed_dt = dt;
     void* params[] = {&a};
     const unsigned grid = (unsigned)((n + INFLX_TR_THREADS - 1) / INFLX_TR_THREADS);
-    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (dq_dn) HIP_TRY(hipMemcpyAsync(buf.dq, dq_dn + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (dq_dn) HIP_TRY(hipMemcpyAsync(d_dq, dq_dn + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
     // every byte 0xff: each double is a NaN, which a sample that its lane never reaches keeps
-    HIP_TRY(hipMemsetAsync(buf.out, 0xff, n * plane_bytes, s));
-    HIP_TRY(hipModuleLaunchKernel(m->tr_init, grid, 1, 1, INFLX_TR_THREADS, 1, 1, 0, s, params, nullptr));
-    // launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
-    for (uint64_t step = 0; step < (uint64_t)max_steps;) {
-      const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
-      a.steps = (uint32_t)k;
-      uint32_t running = 0;
-      HIP_TRY(hipMemsetAsync(buf.running, 0, sizeof(uint32_t), s));
-      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, INFLX_TR_THREADS, 1, 1, 0, s, params, nullptr));
-      HIP_TRY(hipMemcpyAsync(&running, buf.running, sizeof running, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      step += k;
-      if (running == 0) break;
-    }
+    HIP_TRY(hipMemsetAsync(d_out, 0xff, n * plane_bytes, s));
+    HIP_TRY(hipModuleLaunchKernel(tr.fn[kLaneInit], grid, 1, 1, INFLX_TR_THREADS, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(advance, a, grid, INFLX_TR_THREADS, max_steps, s))) return rc;
     // the planes as they are: plane (sample, component) of this pass's lanes is n doubles, B doubles apart in `out`
-    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.out, n * sizeof(double), n * sizeof(double), INFLX_TR_OUT_PLANES * S, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry + (size_t)INFLX_TR_CARRY_NEND * n, n * kBack * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), d_out, n * sizeof(double), n * sizeof(double), INFLX_TR_OUT_PLANES * S, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry + (size_t)INFLX_TR_CARRY_NEND * n, n * kBack * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
@@ -3703,176 +3598,67 @@ int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n
 // ---- mode functions and power spectra (inflx_mode_spectra) ------------------------------------------------------------------------
 namespace {
 
-static_assert(kAbiMajor == INFLX_MD_DEFAULT_ABI_MAJOR, "a modes object reports the core object's ABI major: change both together");
-
-// Load `<artefact>.modes` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
-int need_modes(inflx_model* m) {
-  if (m->md_module) return INFLX_OK;
-  const std::string path = m->path + ".modes";
-  FILE* fh = fopen(path.c_str(), "rb");
-  if (!fh)
-    return fail(INFLX_ERR_SYMBOL, "the mode-function kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_modes() "
-                "(inflatox_amd.background.power_spectra does on first use)", m->path.c_str(), path.c_str());
-  fclose(fh);
-  HIP_TRY(hipSetDevice(m->device));
-  hipModule_t module = nullptr;
-  hipError_t e = hipModuleLoad(&module, path.c_str());
-  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
-  auto bail = [&](int code) {
-    const std::string first = g_last_error;
-    (void)hipModuleUnload(module);
-    g_last_error = first;
-    return code;
-  };
-  uint16_t version[3] = {};
-  uint32_t abi = 0;
-  char tag[128] = {0};
-  int rc;
-  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_MD_ABI", &abi, sizeof abi, true)) ||
-      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
-    return bail(rc);
-  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_MD_ABI_VERSION || m->tag != tag)
-    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
-                     "INFLX_MD_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_MD_ABI_VERSION));
-  const char* names[2] = {"inflx_md_advance_rk4", "inflx_md_advance_rkf"};
-  hipFunction_t init = nullptr, adv[2] = {};
-  if (hipModuleGetFunction(&init, module, "inflx_md_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_md_init", path.c_str()));
-  for (int a = 0; a < 2; ++a)
-    if (hipModuleGetFunction(&adv[a], module, names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a]));
-  m->md_module = module;
-  m->md_init = init;
-  for (int a = 0; a < 2; ++a) m->md_advance[a] = adv[a];
-  note_sf_word(m, module);
-  return INFLX_OK;
-}
-
-static_assert(kAbiMajor == INFLX_TN_DEFAULT_ABI_MAJOR, "a tensor object reports the core object's ABI major: change both together");
-
-// Load `<artefact>.tensor` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
-int need_tensor(inflx_model* m) {
-  if (m->tn_module) return INFLX_OK;
-  const std::string path = m->path + ".tensor";
-  FILE* fh = fopen(path.c_str(), "rb");
-  if (!fh)
-    return fail(INFLX_ERR_SYMBOL, "the tensor-mode kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_tensor() "
-                "(inflatox_amd.background.tensor_spectra does on first use)", m->path.c_str(), path.c_str());
-  fclose(fh);
-  HIP_TRY(hipSetDevice(m->device));
-  hipModule_t module = nullptr;
-  hipError_t e = hipModuleLoad(&module, path.c_str());
-  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
-  auto bail = [&](int code) {
-    const std::string first = g_last_error;
-    (void)hipModuleUnload(module);
-    g_last_error = first;
-    return code;
-  };
-  uint16_t version[3] = {};
-  uint32_t abi = 0;
-  char tag[128] = {0};
-  int rc;
-  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_TN_ABI", &abi, sizeof abi, true)) ||
-      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
-    return bail(rc);
-  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_TN_ABI_VERSION || m->tag != tag)
-    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
-                     "INFLX_TN_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_TN_ABI_VERSION));
-  const char* names[2] = {"inflx_tn_advance_rk4", "inflx_tn_advance_rkf"};
-  hipFunction_t init = nullptr, adv[2] = {};
-  if (hipModuleGetFunction(&init, module, "inflx_tn_init") != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel inflx_tn_init", path.c_str()));
-  for (int a = 0; a < 2; ++a)
-    if (hipModuleGetFunction(&adv[a], module, names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a]));
-  m->tn_module = module;
-  m->tn_init = init;
-  for (int a = 0; a < 2; ++a) m->tn_advance[a] = adv[a];
-  note_sf_word(m, module);
-  return INFLX_OK;
-}
-
-// device buffers of one call, released on every way out
-struct MdBuffers {
-  double *p = nullptr, *init = nullptr, *kappa = nullptr, *target = nullptr, *carry = nullptr, *out = nullptr;
-  uint32_t* running = nullptr;
-  ~MdBuffers() {
-    for (double* d : {p, init, kappa, target, carry, out})
-      if (d) (void)hipFree(d);
-    if (running) (void)hipFree(running);
-  }
-};
-
-// the layouts of the two kinds of lane inflx_mode_spectra runs (csrc/inflx_modes_abi.h, csrc/inflx_tensor_abi.h)
+// the layouts of the two kinds of lane inflx_mode_spectra runs (csrc/inflx_modes_abi.h, csrc/inflx_tensor_abi.h), and their objects
 struct MdLayout {
   using Args = InflxMdArgs;
+  static constexpr Companion kObject = kObjModes;
   static constexpr size_t kThreads = INFLX_MD_THREADS, kOutPlanes = INFLX_MD_OUT_PLANES, kCarryPlanes = INFLX_MD_CARRY_PLANES, kCarryNend = INFLX_MD_CARRY_NEND,
                           kCarryStatus = INFLX_MD_CARRY_STATUS;
 };
 struct TnLayout {
   using Args = InflxTnArgs;
+  static constexpr Companion kObject = kObjTensor;
   static constexpr size_t kThreads = INFLX_TN_THREADS, kOutPlanes = INFLX_TN_OUT_PLANES, kCarryPlanes = INFLX_TN_CARRY_PLANES, kCarryNend = INFLX_TN_CARRY_NEND,
                           kCarryStatus = INFLX_TN_CARRY_STATUS;
 };
 
-// The passes, launches and read-back of inflx_mode_spectra over lanes of layout L, with the init kernel and the advance kernel of
-// the chosen method; the arguments are checked and the object is loaded.
+// inflx_mode_spectra over lanes of layout L, its arguments checked: the object of L, then the passes, launches and read-back.
 template <class L>
-int run_mode_lanes(inflx_model* m, hipFunction_t init_fn, hipFunction_t advance, const double* p, size_t P, size_t n_p, const double* init, size_t B,
-                   const double* kappa, const double* n_target, size_t max_steps, double max_err, double dt, unsigned flags, double* out, double* efolds,
-                   int8_t* status) {
+int run_mode_lanes(inflx_model* m, int method, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* kappa, const double* n_target,
+                   size_t max_steps, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status) {
+  int rc = need_companion(m, L::kObject);
+  if (rc) return rc;
+  const CompanionSlot& obj = m->companion[L::kObject];
+  hipFunction_t advance = obj.fn[kLaneAdvance + (method == INFLX_EOM_RKF ? 1 : 0)];
   hipStream_t s = m->stream;
-  size_t nc_max = std::max<size_t>(1, kBgRowBytes / (L::kOutPlanes * sizeof(double)));
-  if (nc_max > L::kThreads) nc_max -= nc_max % L::kThreads;
-  nc_max = std::min({B, kBgMaxLanes, nc_max});
+  const size_t nc_max = inflx_bg_lanes_per_pass(B, L::kOutPlanes * sizeof(double), L::kThreads);
   constexpr size_t kBack = L::kCarryPlanes - L::kCarryNend;  // the carry planes read back: NEND, STATUS
-  MdBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.init), nc_max * 4 * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.kappa), nc_max * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.target), nc_max * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nc_max * L::kCarryPlanes * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), nc_max * L::kOutPlanes * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_init = nullptr, *d_kappa = nullptr, *d_target = nullptr, *d_carry = nullptr, *d_out = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_kappa, nc_max)) || (rc = dev.array(&d_target, nc_max)) ||
+      (rc = dev.array(&d_carry, nc_max * L::kCarryPlanes)) || (rc = dev.array(&d_out, nc_max * L::kOutPlanes)) || (rc = dev.array(&d_running, 1)))
+    return rc;
   std::vector<double> host_carry(nc_max * kBack);
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     typename L::Args a;
     memset(&a, 0, sizeof a);
-    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
     a.p_stride = P == 1 ? 0 : n_p;
-    a.init = buf.init;
-    a.kappa = buf.kappa;
-    a.n_target = buf.target;
-    a.carry = buf.carry;
-    a.out = buf.out;
-    a.running = buf.running;
+    a.init = d_init;
+    a.kappa = d_kappa;
+    a.n_target = d_target;
+    a.carry = d_carry;
+    a.out = d_out;
+    a.running = d_running;
     a.n = n;
     a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
     a.max_err = max_err;
     a.fixed_dt = dt;
     void* params[] = {&a};
     const unsigned grid = (unsigned)((n + L::kThreads - 1) / L::kThreads);
-    HIP_TRY(hipMemcpyAsync(buf.init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(buf.kappa, kappa + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(buf.target, n_target + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_kappa, kappa + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_target, n_target + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
     // every byte 0xff: each double is a NaN, which a lane that emits nothing keeps
-    HIP_TRY(hipMemsetAsync(buf.out, 0xff, n * L::kOutPlanes * sizeof(double), s));
-    HIP_TRY(hipModuleLaunchKernel(init_fn, grid, 1, 1, L::kThreads, 1, 1, 0, s, params, nullptr));
-    // launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
-    for (uint64_t step = 0; step < (uint64_t)max_steps;) {
-      const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
-      a.steps = (uint32_t)k;
-      uint32_t running = 0;
-      HIP_TRY(hipMemsetAsync(buf.running, 0, sizeof(uint32_t), s));
-      HIP_TRY(hipModuleLaunchKernel(advance, grid, 1, 1, L::kThreads, 1, 1, 0, s, params, nullptr));
-      HIP_TRY(hipMemcpyAsync(&running, buf.running, sizeof running, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      step += k;
-      if (running == 0) break;
-    }
+    HIP_TRY(hipMemsetAsync(d_out, 0xff, n * L::kOutPlanes * sizeof(double), s));
+    HIP_TRY(hipModuleLaunchKernel(obj.fn[kLaneInit], grid, 1, 1, L::kThreads, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(advance, a, grid, L::kThreads, max_steps, s))) return rc;
     // the planes as they are: a plane of this pass's lanes is n doubles, B doubles apart in `out`
-    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.out, n * sizeof(double), n * sizeof(double), L::kOutPlanes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(host_carry.data(), buf.carry + (size_t)L::kCarryNend * n, n * kBack * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), d_out, n * sizeof(double), n * sizeof(double), L::kOutPlanes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry + (size_t)L::kCarryNend * n, n * kBack * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
@@ -3890,134 +3676,36 @@ extern "C" {
 int inflx_mode_spectra(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* kappa, const double* n_target,
                        size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status) {
   INFLX_SERIALISE(m);
-  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the mode functions require a 2-field model (model has %u fields)", m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u parameters (got %zu)", m->name.c_str(), m->n_par, n_p);
-  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
-  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per lane (%zu)", P, B);
-  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
-  if (flags & ~(unsigned)(INFLX_EOM_STOP_AT_END | INFLX_MODES_TENSOR)) return fail(INFLX_ERR_ARG, "unknown flags 0x%x", flags);
-  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
-  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
-  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  const int rc = check_integrator_args(m, "the mode functions require", "lane", p, P, n_p, B, method, flags, INFLX_EOM_STOP_AT_END | INFLX_MODES_TENSOR, max_steps, max_err, dt,
+                                       status);
+  if (rc) return rc;
   if (B == 0) return INFLX_OK;
   if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
   if (!kappa) return fail(INFLX_ERR_ARG, "kappa array is NULL");
   if (!n_target) return fail(INFLX_ERR_ARG, "n_target array is NULL");
   if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
   HIP_TRY(hipSetDevice(m->device));
-  const int mi = method == INFLX_EOM_RKF ? 1 : 0;
-  if (flags & INFLX_MODES_TENSOR) {
-    const int rc = need_tensor(m);
-    if (rc) return rc;
-    return run_mode_lanes<TnLayout>(m, m->tn_init, m->tn_advance[mi], p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
-  }
-  int rc = need_modes(m);
-  if (rc) return rc;
-  return run_mode_lanes<MdLayout>(m, m->md_init, m->md_advance[mi], p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
+  if (flags & INFLX_MODES_TENSOR) return run_mode_lanes<TnLayout>(m, method, p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
+  return run_mode_lanes<MdLayout>(m, method, p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
 }
 
 }  // extern "C"
 
 // ---- delta-N stencils: derivatives of N and local f_NL (inflx_delta_n) -------------------------------------------------------------
-namespace {
-
-static_assert(kAbiMajor == INFLX_DN_DEFAULT_ABI_MAJOR, "a delta-N object reports the core object's ABI major: change both together");
-
-// Load `<artefact>.deltan` beside the core object: it must carry the core object's MODEL_TAG and this library's layout word.
-int need_deltan(inflx_model* m) {
-  if (m->dn_module) return INFLX_OK;
-  const std::string path = m->path + ".deltan";
-  FILE* fh = fopen(path.c_str(), "rb");
-  if (!fh)
-    return fail(INFLX_ERR_SYMBOL, "the delta-N kernels of %s are not loaded and no %s exists: build it with CompilationArtifact.ensure_deltan() "
-                "(inflatox_amd.background.delta_N does on first use)", m->path.c_str(), path.c_str());
-  fclose(fh);
-  HIP_TRY(hipSetDevice(m->device));
-  hipModule_t module = nullptr;
-  hipError_t e = hipModuleLoad(&module, path.c_str());
-  if (e != hipSuccess) return fail(INFLX_ERR_IO, "could not load %s as a gfx950 code object: %s", path.c_str(), hipGetErrorString(e));
-  auto bail = [&](int code) {
-    const std::string first = g_last_error;
-    (void)hipModuleUnload(module);
-    g_last_error = first;
-    return code;
-  };
-  uint16_t version[3] = {};
-  uint32_t abi = 0;
-  char tag[128] = {0};
-  int rc;
-  if ((rc = read_global_of(module, path.c_str(), "VERSION", version, sizeof version, true)) || (rc = read_global_of(module, path.c_str(), "INFLX_DN_ABI", &abi, sizeof abi, true)) ||
-      (rc = read_global_of(module, path.c_str(), "MODEL_TAG", tag, sizeof tag - 1, false)))
-    return bail(rc);
-  if (version[0] != m->version[0] || version[1] != m->version[1] || abi != INFLX_DN_ABI_VERSION || m->tag != tag)
-    return bail(fail(INFLX_ERR_VERSION, "%s does not belong to artefact %s: built from another model, with other options or for another layout (tag \"%s\", expected \"%s\"; "
-                     "INFLX_DN_ABI %u, expected %u)", path.c_str(), m->path.c_str(), tag, m->tag.c_str(), abi, (unsigned)INFLX_DN_ABI_VERSION));
-  const char* names[6] = {"inflx_dn_init", "inflx_dn_reduce", "inflx_dn_end_rk4", "inflx_dn_end_rkf", "inflx_dn_surface_rk4", "inflx_dn_surface_rkf"};
-  hipFunction_t fn[6] = {};
-  for (int a = 0; a < 6; ++a)
-    if (hipModuleGetFunction(&fn[a], module, names[a]) != hipSuccess) return bail(fail(INFLX_ERR_SYMBOL, "%s lacks kernel %s", path.c_str(), names[a]));
-  m->dn_module = module;
-  m->dn_init = fn[0];
-  m->dn_reduce = fn[1];
-  for (int a = 0; a < 2; ++a) {
-    m->dn_end[a] = fn[2 + a];
-    m->dn_surface[a] = fn[4 + a];
-  }
-  note_sf_word(m, module);
-  return INFLX_OK;
-}
-
-// device buffers of one call, released on every way out
-struct DnBuffers {
-  double *p = nullptr, *centre = nullptr, *vel = nullptr, *carry_a = nullptr, *carry = nullptr, *hc = nullptr, *out = nullptr;
-  uint32_t* running = nullptr;
-  ~DnBuffers() {
-    for (double* d : {p, centre, vel, carry_a, carry, hc, out})
-      if (d) (void)hipFree(d);
-    if (running) (void)hipFree(running);
-  }
-};
-
-// launches of at most INFLX_BG_STEPS_PER_LAUNCH accepted steps until the steps run out or a launch leaves no lane running
-int dn_advance(hipFunction_t fn, InflxDnArgs& a, size_t lanes, size_t max_steps, uint32_t* d_running, hipStream_t s) {
-  void* params[] = {&a};
-  const unsigned grid = (unsigned)((lanes + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS);
-  for (uint64_t step = 0; step < (uint64_t)max_steps;) {
-    const uint64_t k = std::min<uint64_t>((uint64_t)max_steps - step, INFLX_BG_STEPS_PER_LAUNCH);
-    a.steps = (uint32_t)k;
-    uint32_t running = 0;
-    HIP_TRY(hipMemsetAsync(d_running, 0, sizeof(uint32_t), s));
-    HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
-    HIP_TRY(hipMemcpyAsync(&running, d_running, sizeof running, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    step += k;
-    if (running == 0) break;
-  }
-  return INFLX_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int inflx_delta_n(inflx_model* m, const double* p, size_t P, size_t n_p, const double* centre, size_t B, const double* vel, int rule, double h0, double h1,
                   const double* h_end, size_t max_steps, int method, double max_err, double dt, double* out, double* surface, int32_t* status) {
   INFLX_SERIALISE(m);
-  if (!m) return fail(INFLX_ERR_ARG, "model handle is NULL");
-  if (m->dim != 2) return fail(INFLX_ERR_SHAPE, "the delta-N expansion requires a 2-field model (model has %u fields)", m->dim);
-  if (n_p != m->n_par) return fail(INFLX_ERR_SHAPE, "model \"%s\" has %u parameters (got %zu)", m->name.c_str(), m->n_par, n_p);
-  if (!p && n_p) return fail(INFLX_ERR_ARG, "parameter array is NULL");
-  if (P != 1 && P != B) return fail(INFLX_ERR_SHAPE, "parameter rows: %zu, expected 1 or one per stencil (%zu)", P, B);
-  if (method != INFLX_EOM_RK4 && method != INFLX_EOM_RKF) return fail(INFLX_ERR_ARG, "unknown integration method %d", method);
-  if (rule != INFLX_DN_VELOCITY_FIXED && rule != INFLX_DN_VELOCITY_SLOW_ROLL && rule != INFLX_DN_VELOCITY_EXPLICIT) return fail(INFLX_ERR_ARG, "unknown velocity rule %d", rule);
-  if ((rule == INFLX_DN_VELOCITY_EXPLICIT) != (vel != nullptr) && B) return fail(INFLX_ERR_ARG, "the member velocities go with the explicit rule, and only with it");
-  if (!(h0 > 0.0) || !std::isfinite(h0) || !(h1 > 0.0) || !std::isfinite(h1)) return fail(INFLX_ERR_ARG, "the stencil steps must be positive finite numbers");
-  if ((uint64_t)max_steps > (UINT64_C(1) << 62)) return fail(INFLX_ERR_ARG, "max_steps exceeds 2^62 accepted steps");
-  if (!(max_err > 0.0) || !std::isfinite(max_err)) return fail(INFLX_ERR_ARG, "max_err must be a positive finite number");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(INFLX_ERR_ARG, "dt must be 0 (adaptive) or a positive finite step");
-  if (!status) return fail(INFLX_ERR_ARG, "status pointer is NULL");
+  auto stencil = [&]() -> int {
+    if (rule != INFLX_DN_VELOCITY_FIXED && rule != INFLX_DN_VELOCITY_SLOW_ROLL && rule != INFLX_DN_VELOCITY_EXPLICIT) return fail(INFLX_ERR_ARG, "unknown velocity rule %d", rule);
+    if ((rule == INFLX_DN_VELOCITY_EXPLICIT) != (vel != nullptr) && B) return fail(INFLX_ERR_ARG, "the member velocities go with the explicit rule, and only with it");
+    if (!(h0 > 0.0) || !std::isfinite(h0) || !(h1 > 0.0) || !std::isfinite(h1)) return fail(INFLX_ERR_ARG, "the stencil steps must be positive finite numbers");
+    return INFLX_OK;
+  };
+  // (the call has no flags)
+  int rc = check_integrator_args(m, "the delta-N expansion requires", "stencil", p, P, n_p, B, method, 0, 0, stencil, max_steps, max_err, dt, status);
+  if (rc) return rc;
   if (h_end)
     for (size_t b = 0; b < B; ++b)
       if (!(h_end[b] > 0.0) || !std::isfinite(h_end[b])) return fail(INFLX_ERR_ARG, "h_end %zu is not a positive finite number", b);
@@ -4025,34 +3713,33 @@ int inflx_delta_n(inflx_model* m, const double* p, size_t P, size_t n_p, const d
   if (!centre) return fail(INFLX_ERR_ARG, "centre array is NULL");
   if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
   HIP_TRY(hipSetDevice(m->device));
-  int rc = need_deltan(m);
-  if (rc) return rc;
+  if ((rc = need_companion(m, kObjDeltan))) return rc;
+  const CompanionSlot& dn = m->companion[kObjDeltan];
   hipStream_t s = m->stream;
   const int mi = method == INFLX_EOM_RKF ? 1 : 0;
   // a pass holds whole stencils: its 9 nb lanes stay within the lane bound of a pass of the solver
   const size_t nb_max = std::min(B, std::max<size_t>(1, kBgMaxLanes / 9));
-  DnBuffers buf;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.p), std::max<size_t>(1, P * n_p) * sizeof(double)));
-  if (P * n_p) HIP_TRY(hipMemcpyAsync(buf.p, p, P * n_p * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.centre), nb_max * 4 * sizeof(double)));
-  if (vel) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.vel), nb_max * 18 * sizeof(double)));
-  if (!h_end) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry_a), nb_max * INFLX_DN_CARRY_PLANES * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.carry), nb_max * 9 * INFLX_DN_CARRY_PLANES * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.hc), nb_max * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.out), nb_max * INFLX_DN_OUT_PLANES * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf.running), sizeof(uint32_t)));
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_centre = nullptr, *d_vel = nullptr, *d_carry_a = nullptr, *d_carry = nullptr, *d_hc = nullptr, *d_out = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_centre, nb_max * 4)) || (vel && (rc = dev.array(&d_vel, nb_max * 18))) ||
+      (!h_end && (rc = dev.array(&d_carry_a, nb_max * INFLX_DN_CARRY_PLANES))) || (rc = dev.array(&d_carry, nb_max * 9 * INFLX_DN_CARRY_PLANES)) ||
+      (rc = dev.array(&d_hc, nb_max)) || (rc = dev.array(&d_out, nb_max * INFLX_DN_OUT_PLANES)) || (rc = dev.array(&d_running, 1)))
+    return rc;
+  // the workgroups of a launch over `lanes` lanes
+  auto grid_of = [](size_t lanes) { return (unsigned)((lanes + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS); };
   std::vector<double> host_status(nb_max), host_surface(2 * nb_max);
 
   for (size_t c0 = 0; c0 < B; c0 += nb_max) {
     const size_t nb = std::min(nb_max, B - c0);
     InflxDnArgs a;
     memset(&a, 0, sizeof a);
-    a.p = buf.p + (P == 1 ? 0 : c0 * n_p);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
     a.p_stride = P == 1 ? 0 : n_p;
-    a.centre = buf.centre;
-    a.vel = buf.vel;
-    a.hc = buf.hc;
-    a.running = buf.running;
+    a.centre = d_centre;
+    a.vel = d_vel;
+    a.hc = d_hc;
+    a.running = d_running;
     a.nb = nb;
     a.rule = (uint32_t)rule;
     a.h0 = h0;
@@ -4060,42 +3747,42 @@ int inflx_delta_n(inflx_model* m, const double* p, size_t P, size_t n_p, const d
     a.max_err = max_err;
     a.fixed_dt = dt;
     void* params[] = {&a};
-    HIP_TRY(hipMemcpyAsync(buf.centre, centre + c0 * 4, nb * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (vel) HIP_TRY(hipMemcpyAsync(buf.vel, vel + c0 * 18, nb * 18 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_centre, centre + c0 * 4, nb * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (vel) HIP_TRY(hipMemcpyAsync(d_vel, vel + c0 * 18, nb * 18 * sizeof(double), hipMemcpyHostToDevice, s));
     if (h_end) {
-      HIP_TRY(hipMemcpyAsync(buf.hc, h_end + c0, nb * sizeof(double), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(d_hc, h_end + c0, nb * sizeof(double), hipMemcpyHostToDevice, s));
     } else {
       // phase A, the centres alone: every byte 0xff is a NaN, which a centre that finds no surface keeps
-      HIP_TRY(hipMemsetAsync(buf.hc, 0xff, nb * sizeof(double), s));
-      a.carry = buf.carry_a;
+      HIP_TRY(hipMemsetAsync(d_hc, 0xff, nb * sizeof(double), s));
+      a.carry = d_carry_a;
       a.members = 1;
-      HIP_TRY(hipModuleLaunchKernel(m->dn_init, (unsigned)((nb + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
-      if ((rc = dn_advance(m->dn_end[mi], a, nb, max_steps, buf.running, s))) return rc;
+      HIP_TRY(hipModuleLaunchKernel(dn.fn[kDnInit], grid_of(nb), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
+      if ((rc = advance_until_done(dn.fn[kDnEnd + mi], a, grid_of(nb), INFLX_DN_THREADS, max_steps, s))) return rc;
     }
     // phase B, all nine members
     const size_t lanes = 9 * nb;
-    a.carry = buf.carry;
+    a.carry = d_carry;
     a.members = 9;
-    HIP_TRY(hipModuleLaunchKernel(m->dn_init, (unsigned)((lanes + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
-    if ((rc = dn_advance(m->dn_surface[mi], a, lanes, max_steps, buf.running, s))) return rc;
+    HIP_TRY(hipModuleLaunchKernel(dn.fn[kDnInit], grid_of(lanes), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(dn.fn[kDnSurface + mi], a, grid_of(lanes), INFLX_DN_THREADS, max_steps, s))) return rc;
     InflxDnReduceArgs r;
     memset(&r, 0, sizeof r);
     r.p = a.p;
     r.p_stride = a.p_stride;
-    r.centre = buf.centre;
-    r.carry = buf.carry;
-    r.status_a = h_end ? nullptr : buf.carry_a + (size_t)INFLX_DN_CARRY_STATUS * nb;
-    r.out = buf.out;
+    r.centre = d_centre;
+    r.carry = d_carry;
+    r.status_a = h_end ? nullptr : d_carry_a + (size_t)INFLX_DN_CARRY_STATUS * nb;
+    r.out = d_out;
     r.nb = nb;
     r.h0 = h0;
     r.h1 = h1;
     void* rparams[] = {&r};
-    HIP_TRY(hipModuleLaunchKernel(m->dn_reduce, (unsigned)((nb + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, rparams, nullptr));
+    HIP_TRY(hipModuleLaunchKernel(dn.fn[kDnReduce], grid_of(nb), 1, 1, INFLX_DN_THREADS, 1, 1, 0, s, rparams, nullptr));
     // the planes as they are: a plane of this pass's stencils is nb doubles, B doubles apart in `out`
-    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), buf.out, nb * sizeof(double), nb * sizeof(double), INFLX_DN_OUT_PLANES, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(host_status.data(), buf.out + (size_t)(INFLX_DN_OUT_PLANES - 1) * nb, nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(host_surface.data(), buf.hc, nb * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (!h_end) HIP_TRY(hipMemcpyAsync(host_surface.data() + nb, buf.carry_a + (size_t)INFLX_DN_CARRY_RESULT * nb, nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), d_out, nb * sizeof(double), nb * sizeof(double), INFLX_DN_OUT_PLANES, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_status.data(), d_out + (size_t)(INFLX_DN_OUT_PLANES - 1) * nb, nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_surface.data(), d_hc, nb * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (!h_end) HIP_TRY(hipMemcpyAsync(host_surface.data() + nb, d_carry_a + (size_t)INFLX_DN_CARRY_RESULT * nb, nb * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t l = 0; l < nb; ++l) {
       status[c0 + l] = (int32_t)host_status[l];

@@ -1,13 +1,15 @@
 // The row transpose on the CPU (csrc/inflx_background_rows.h): every thread of every workgroup of a launch through the load phase,
 // then every thread through the store phase -- what inflx_bg_rows_transpose does around its __syncthreads() --, on heap blocks of
 // exactly the sizes the kernel is promised, so that an AddressSanitizer build sees any access outside them; and the plan of a
-// call's lane passes.  Built and run by tests/test_background_rows.py.  Exit status 0: every check passed.
+// call's lane passes, with the lanes of a pass whose buffer holds whole lanes (csrc/inflx_background_passes.h).  Built and run by
+// tests/test_background_rows.py.  Exit status 0: every check passed.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "inflx_background_passes.h"
 #include "inflx_background_rows.h"
 
 namespace {
@@ -101,6 +103,11 @@ void check_plan(size_t B, size_t rows, bool force, bool transposed, size_t lanes
         (int)force, p.lanes_per_pass, (int)p.transposed, lanes, (int)transposed);
 }
 
+void check_lanes(size_t B, size_t bytes_per_lane, size_t threads, size_t lanes) {
+  const size_t got = inflx_bg_lanes_per_pass(B, bytes_per_lane, threads);
+  CHECK(got == lanes, "lanes_per_pass(B %zu, %zu bytes per lane, %zu threads) = %zu, expected %zu", B, bytes_per_lane, threads, got, lanes);
+}
+
 }  // namespace
 
 int main() {
@@ -145,6 +152,15 @@ int main() {
     const InflxBgRowsPlan p = inflx_bg_rows_plan(M, rows, false);
     CHECK(p.transposed && p.lanes_per_pass * rows * 56 <= (size_t(2) << 30), "rows %zu: %zu lanes", rows, p.lanes_per_pass);
   }
+  // the lanes of a pass whose 256 MiB buffer holds `bytes_per_lane` of every lane: whole workgroups where more than one fits
+  const size_t big = 10000000;
+  check_lanes(65541, 4096, 256, 65536);                // S = 64 samples of 8 doubles: two passes
+  check_lanes(big, 5120, 256, 52224);                  // floor(2^28 / 5120) = 52 428, whole workgroups
+  check_lanes(big, size_t(1) << 29, 256, 1);           // a lane larger than the buffer: one at a time
+  check_lanes(big, 894784, 256, 256);                  // quotient 300
+  check_lanes(big, 1342177, 256, 200);                 // quotient 200, below one workgroup: not rounded
+  check_lanes(5, 4096, 256, 5);                        // no more than the call has
+  check_lanes(M + 257, 176, 256, M);                   // no more than kBgMaxLanes
   if (g_failures) {
     std::fprintf(stderr, "%d checks failed\n", g_failures);
     return 1;

@@ -280,3 +280,34 @@ def test_deltan_object_of_another_layout_is_refused(bg):
         for path in (stale, *headers):
             if os.path.exists(path):
                 os.remove(path)
+
+
+@pytest.mark.parametrize("h_end", [None, 0.55], ids=["both-phases", "H_end"])
+def test_more_than_one_pass_lands_behind_the_first_in_every_plane(bg, hyper, h_end):
+    """A pass holds floor(2^20 / 9) = 116 508 stencils: B = 116 508 + 3 takes two, five fixed steps of dt = 0.1 each from centres
+    0.1 e-folds before the end of inflation (H = 0.55 there), once with the centres' own search for the surface and once with
+    ``H_end`` given.  The first five stencils, those on either side of the seam and the last five are the same stencils run alone,
+    bit for bit and NaN where NaN, in ``out``, ``surface`` and ``status`` of ``InflatoxDevLib.delta_n``; stencils on both sides of
+    the seam are LOCATED."""
+    from inflatox_amd import _native
+
+    first, B = 116_508, 116_508 + 3
+    rng = np.random.default_rng(6)
+    x = np.stack([rng.uniform(2.2, 2.3, B), rng.uniform(-1, 1, B)], axis=1)
+    v = np.stack([-(x[:, 0] - 1) / (3 * np.sqrt((x[:, 0] - 1) ** 2 / 6)), rng.uniform(-1e-2, 1e-2, B)], axis=1)
+    centre = np.concatenate([x, v], axis=1)
+    hyper.artifact.ensure_deltan()
+    lib = bg._dylib(hyper.artifact, background=False)
+
+    def run(sl):
+        surface = None if h_end is None else np.full(len(centre[sl]), h_end)
+        return lib.delta_n(hyper.p, np.ascontiguousarray(centre[sl]), None, _native.DN_FIXED, H, H, surface, 5, _native.EOM_RKF, 1e-10, 0.1)
+
+    out, surface, status = run(slice(None))
+    print(f"statuses {np.unique(status, return_counts=True)}")
+    assert out.shape == (21, B) and surface.shape == (2, B) and status.shape == (B,)
+    assert (status[first - 3 : first] == LOCATED).any() and (status[first:] == LOCATED).any() and np.isfinite(out[:, status == LOCATED]).all()
+    assert np.isnan(surface[1]).all() if h_end else np.isfinite(surface[:, status == LOCATED]).all()
+    for sl in (slice(0, 5), slice(first - 3, first + 3), slice(B - 5, B)):
+        o, s, st = run(sl)
+        assert np.array_equal(out[:, sl], o, equal_nan=True) and np.array_equal(surface[:, sl], s, equal_nan=True) and np.array_equal(status[sl], st), sl

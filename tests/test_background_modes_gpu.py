@@ -278,3 +278,26 @@ def test_modes_object_of_another_layout_is_refused(bg):
         for path in (stale, *headers):
             if os.path.exists(path):
                 os.remove(path)
+
+
+def test_more_than_one_pass_is_the_same_lanes_run_alone(bg, hyper):
+    """n = 2^20 + 257 scalar lanes -- a pass holds at most 2^20 --, two fixed steps of dt = 0.01, as in
+    tests/test_background_tensor_gpu.py: every lane with a target of 0.02 e-folds reaches it within them (TARGET, values emitted), the
+    others run out of steps (COMPLETE, NaN).  The first five lanes, the lanes on either side of the seam and the last five are the
+    same lanes run alone, bit for bit and NaN where NaN, in every returned array; lanes on both sides of the seam hold values."""
+    p, art, _twin = hyper
+    n, first = (1 << 20) + 257, 1 << 20
+    rng = np.random.default_rng(5)
+    x = np.stack([rng.uniform(4.5, 5.0, n), rng.uniform(-1.0, 1.0, n)], axis=1)
+    init = np.concatenate([x, np.stack([np.full(n, -0.8), rng.uniform(-1e-3, 1e-3, n)], axis=1)], axis=1)
+    kappa = rng.uniform(2.0, 6.0, n)
+    target = np.where(np.arange(n) % 3 == 2, np.nan, 0.02)
+    kw = dict(max_steps=2, dt=0.01)
+    whole = _lanes(bg, art, p, init, kappa, target, **kw)
+    assert whole.out.shape == (22, n) and np.array_equal(whole.status, np.where(np.isnan(target), COMPLETE, TARGET))
+    assert np.isfinite(whole.out[:, whole.status == TARGET]).all() and np.isnan(whole.out[:, whole.status == COMPLETE]).all()
+    assert (whole.status[first - 3 : first] == TARGET).any() and (whole.status[first : first + 3] == TARGET).any()
+    for sl in (slice(0, 5), slice(first - 3, first + 3), slice(n - 5, n)):
+        alone = _lanes(bg, art, p, init[sl], kappa[sl], target[sl], **kw)
+        for a, b in zip(whole[:3], alone[:3]):
+            assert np.array_equal(a[..., sl], b, equal_nan=True), sl

@@ -213,3 +213,25 @@ def test_stale_background_object_is_refused():
         for path in (stale, hdr, eom_hdr):
             if os.path.exists(path):
                 os.remove(path)
+
+
+def test_more_than_one_pass_lands_behind_the_first(bg):
+    """B = 2^20 + 3 -- a pass holds at most 2^20 lanes --, three fixed steps of dt = 0.01 from inflating states of the hyperbolic
+    model: two lanes in three have a target of 0.004 e-folds, which they reach (TARGET), the third one of 1, which it does not
+    (COMPLETE, NaN).  The first five lanes, the lanes on either side of the seam and the last five are the same lanes run alone,
+    bit for bit and NaN where NaN, in every member; lanes on both sides of the seam hold a located state."""
+    from transfer_reference import hyper_states
+
+    spec, art = workloads.artifact_for("hyperbolic")
+    first, B = 1 << 20, (1 << 20) + 3
+    x, v = hyper_states(B, seed=12)
+    targets = np.where(np.arange(B) % 3 == 2, 1.0, 0.004)
+    kw = dict(max_steps=3, solver="rkf", dt=0.01)
+    big = bg.state_at_efolds(art, spec.args, x, v, targets, **kw)
+    assert np.array_equal(big.status, np.where(targets == 1.0, COMPLETE, TARGET)), np.bincount(big.status)
+    assert np.isfinite(big.state[big.status == TARGET]).all() and np.isnan(big.state[big.status == COMPLETE]).all()
+    assert np.isfinite(big.state[first - 3 : first]).any() and np.isfinite(big.state[first:]).any()
+    for sl in (slice(0, 5), slice(first - 3, first + 3), slice(B - 5, B)):
+        small = bg.state_at_efolds(art, spec.args, x[sl], v[sl], targets[sl], **kw)
+        for f in FIELDS:
+            assert np.array_equal(getattr(big, f)[sl], getattr(small, f), equal_nan=True), (sl, f)

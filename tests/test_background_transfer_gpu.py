@@ -273,3 +273,21 @@ def test_plane_against_the_field_basis_system(bg):
     err, bound = tr.plane_error(got, cs, a, b), tr.plane_bound("rkf", 1e-8)
     print(f"plane: worst |GPU - truth (a)| {err:.3e} (bound {bound:.3e})")
     assert err <= bound
+
+
+def test_more_than_one_pass_lands_behind_the_first_in_every_plane(bg, hyper):
+    """S = 64 samples are 64 x 10 doubles per lane, so the 256 MiB sample buffer holds floor(2^28 / 5120) = 52 428 lanes, whole
+    workgroups of 256: 52 224.  B = 52 224 + 5 takes two passes, five fixed steps of dt = 1e-3 each, and the second one's five lanes
+    land behind the first one's in every plane of the result: the first five lanes, the lanes on either side of the seam and the
+    last five are the same lanes run alone, bit for bit and NaN where NaN.  The first sample is N = 0, which every lane stores."""
+    p, art, _twin = hyper
+    first, B = 52_224, 52_224 + 5
+    x, v = tr.hyper_states(B, seed=4)
+    samples = np.linspace(0.0, 3e-3, 64)
+    kw = dict(max_steps=5, solver="rkf", dt=1e-3, stop_at_end=False)
+    big = bg.transfer_functions(art, p, samples, x, v, **kw)
+    assert big.T_SS.shape == (B, 64) and np.all(big.n_stored >= 1) and np.all(big.T_SS[:, 0] == 1.0) and np.isfinite(big.states[:, 0]).all()
+    print(f"n_stored {big.n_stored.min()} .. {big.n_stored.max()}, statuses {np.bincount(big.status)}")
+    assert big.n_stored.max() > 1 and np.isfinite(big.T_RS[first - 2 : first + 2, 1]).all()
+    for sl in (slice(0, 5), slice(first - 2, first + 2), slice(B - 5, B)):
+        assert _same(big, bg.transfer_functions(art, p, samples, x[sl], v[sl], **kw), sl), sl
