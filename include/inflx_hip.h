@@ -672,5 +672,7 @@ int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p
 
 /* the delta-N expansion (derivatives of N with respect to the initial fields, local f_NL): its entry point is declared in a header of its own */
 #include "inflx_hip_deltan.h"
+/* the spectra of a mode sampled along its evolution (inflx_mode_spectra with samples): likewise */
+#include "inflx_hip_evolution.h"
 
 #endif /* INFLX_HIP_H */

@@ -142,6 +142,14 @@ DELTAN_SIGNATURES = {
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, C.c_int, C.c_double, C.c_double, _DP, _SIZE, C.c_int, C.c_double, C.c_double, _DP, _DP, C.POINTER(C.c_int32)],
     ),
 }
+# ... and for include/inflx_hip_evolution.h
+EVOLUTION_SIGNATURES = {
+    "inflx_mode_evolution": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _DP, _DP, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, C.POINTER(C.c_int8)],
+    ),
+}
+EV_SAMPLE_PLANES = 6
 DN_FIXED, DN_SLOW_ROLL, DN_EXPLICIT = 0, 1, 2  # inflx_dn_velocity
 DN_LOCATED, DN_PAST_SURFACE = 7, 8  # inflx_dn_status
 DN_OUT_PLANES = 21
@@ -158,7 +166,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -214,7 +222,7 @@ def load_library():
             )
         _preload_hip_runtime()
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items(), *EVOLUTION_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -673,6 +681,39 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return out, efolds, status
+
+    # ---- spectra of a mode along its evolution (include/inflx_hip_evolution.h: inflx_mode_evolution)
+    def mode_evolution(self, p, init, kappa, n_target, shift, samples, max_steps: int, method: int, max_err: float, dt: float, flags: int):
+        """``mode_spectra``'s scalar lanes with samples: each lane also returns its spectra at the local e-fold counts
+        ``samples[k] - shift[lane]`` (``samples`` (S,), strictly increasing, shared; ``shift`` (n,)).  Returns (out (22, n), efolds,
+        status) as ``mode_spectra`` does -- bit for bit its values for the same lanes -- and sampled (S, 6, n): P_R, P_S, C_RS, the
+        local N, the local t and epsilon_H, lane fastest, NaN for a sample the lane did not pass.  ``flags``: ``EOM_STOP_AT_END`` or 0.
+        The evolution object must be in place (``CompilationArtifact.ensure_evolution``)."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        kappa = _f64(kappa, "kappa")
+        n_target = _f64(n_target, "n_target")
+        shift = _f64(shift, "shift")
+        samples = _f64(samples, "samples")
+        n = init.shape[0]
+        if kappa.shape != (n,) or n_target.shape != (n,) or shift.shape != (n,):
+            raise InflatoxShapeError(f"kappa, n_target and shift must have shape ({n},) (got {kappa.shape}, {n_target.shape} and {shift.shape})")
+        if samples.ndim != 1:
+            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        S = samples.shape[0]
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((22, n))
+        sampled = np.empty((S, EV_SAMPLE_PLANES, n))
+        efolds = np.empty(n)
+        status = np.empty(n, dtype=np.int8)
+        _check(
+            self._lib.inflx_mode_evolution(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), n, _ptr(kappa), _ptr(n_target), _ptr(shift), _ptr(samples), S, int(max_steps), int(method),
+                float(max_err), float(dt), int(flags), _ptr(out), _ptr(sampled), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+            )
+        )  # fmt: skip
+        return out, sampled, efolds, status
 
     # ---- delta-N stencils (include/inflx_hip_deltan.h: inflx_delta_n) -----------------------------
     def delta_n(self, p, centre, vel, rule: int, h0: float, h1: float, h_end, max_steps: int, method: int, max_err: float, dt: float):

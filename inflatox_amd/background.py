@@ -25,7 +25,9 @@ own -- the scalar tilt n_s, its running, the tensor tilt n_t and the tensor-to-s
 ``horizon_exit_map`` followed by it: n_s and r, as maps, of the mode that leaves the horizon N_star e-folds before the end of inflation.
 ``delta_N`` runs nine-trajectory stencils around given states to one surface of uniform density each and differences the e-fold counts
 -- N_,I, N_,IJ, the covariant second derivative and the local non-Gaussianity f_NL of the delta-N expansion -- and ``fnl_map`` is
-``horizon_exit_map`` followed by it.
+``horizon_exit_map`` followed by it.  ``spectra_evolution`` is ``power_spectra`` with every mode's spectra sampled at a list of e-fold counts
+along its evolution, from one integration of every lane; ``evolution_map`` is ``horizon_exit_map`` followed by it, and
+``transfer_from_spectra`` reads the transfer functions T_RS and T_SS off such samples: the measured counterpart of ``transfer_functions``.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -52,7 +54,7 @@ from .compiler import CompilationArtifact
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
            "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses", "transfer_functions", "transfer_map",
            "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra", "tensor_spectra", "TensorSpectra", "observables", "Observables", "observables_map",
-           "delta_N", "DeltaN", "fnl_map", "delta_N_status"]  # fmt: skip
+           "delta_N", "DeltaN", "fnl_map", "delta_N_status", "spectra_evolution", "SpectraEvolution", "evolution_map", "transfer_from_spectra"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -783,6 +785,27 @@ def _mode_lanes(artifact, tensor, p, n_exit, x, v, N_eval, N_sub, max_steps, max
     arguments: (out (planes, B K) with NaN for a lane that did not stop where asked, h_exit (B, K), n_exit, lane_start (B K,),
     n_end (B K,), status (B K,))."""
     B, K = x.shape[0], n_exit.size
+    h_exit, status, run, lane_start, lane_p, init, kappa, target = _mode_stage1(artifact, p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
+    out = np.full((8 if tensor else 22, B * K), np.nan)
+    n_end = np.full(B * K, np.nan)
+    if run.size:
+        if tensor:
+            artifact.ensure_tensor()
+        else:
+            artifact.ensure_modes()
+        lib = _dylib(artifact, background=False)
+        flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.MODES_TENSOR if tensor else 0)
+        got, ends, st = lib.mode_spectra(lane_p, init, kappa, target, max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
+        _mode_stage2_result(out, n_end, status, run, N_eval, got, ends, st)
+    return out, h_exit, n_exit, lane_start, n_end, status
+
+
+def _mode_stage1(artifact, p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end):
+    """Stage 1 of ``power_spectra``, ``tensor_spectra`` and ``spectra_evolution`` and the lanes of their stage 2: (h_exit (B, K),
+    status (B K,) of stage 1, run -- the lanes b K + j whose start state and exit were found --, lane_start (B K,), and for the lanes
+    of ``run``: parameter rows, init (n, 4), kappa (n,), n_target (n,) -- NaN without ``N_eval``)."""
+    K = n_exit.size
+    B = x.shape[0]
     starts = n_exit - N_sub
     pts, inverse = np.unique(np.concatenate([starts, n_exit]), return_inverse=True)
     bg = solve_eom_sampled(artifact, p, pts, x, v, max_steps, max_err, solver, dt=dt, stop_at_end=stop_at_end)
@@ -790,26 +813,20 @@ def _mode_lanes(artifact, tensor, p, n_exit, x, v, N_eval, N_sub, max_steps, max
     h_exit = bg.states[:, inverse[K:], 4]  # (B, K)
     kappa = h_exit * math.exp(N_sub)
     status = np.repeat(bg.status[:, None], K, axis=1).reshape(-1)
-    out = np.full((8 if tensor else 22, B * K), np.nan)
-    n_end = np.full(B * K, np.nan)
     run = np.flatnonzero((np.isfinite(start).all(axis=2) & np.isfinite(h_exit)).reshape(-1))
     lane_start = np.tile(starts, B)
-    if run.size:
-        target = np.full(run.size, np.nan) if N_eval is None else N_eval - lane_start[run]
-        if tensor:
-            artifact.ensure_tensor()
-        else:
-            artifact.ensure_modes()
-        lib = _dylib(artifact, background=False)
-        lane_p = p if p.ndim == 1 else np.ascontiguousarray(np.repeat(p, K, axis=0)[run])
-        flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.MODES_TENSOR if tensor else 0)
-        got, ends, st = lib.mode_spectra(lane_p, np.ascontiguousarray(start.reshape(-1, 4)[run]), np.ascontiguousarray(kappa.reshape(-1)[run]), target, max_steps,
-                                         _METHODS[solver], max_err, dt or 0.0, flags)  # fmt: skip
-        valid = st == (ENDED if N_eval is None else TARGET)
-        out[:, run] = np.where(valid[None, :], got, np.nan)
-        n_end[run] = np.where(st == ENDED, ends, np.nan)
-        status[run] = st
-    return out, h_exit, n_exit, lane_start, n_end, status
+    target = np.full(run.size, np.nan) if N_eval is None else N_eval - lane_start[run]
+    lane_p = p if p.ndim == 1 else np.ascontiguousarray(np.repeat(p, K, axis=0)[run])
+    return h_exit, status, run, lane_start, lane_p, np.ascontiguousarray(start.reshape(-1, 4)[run]), np.ascontiguousarray(kappa.reshape(-1)[run]), target
+
+
+def _mode_stage2_result(out, n_end, status, run, N_eval, got, ends, st):
+    """What stage 2 returned for the lanes ``run``, put into the lanes' arrays: the values of a lane that stopped where it was asked
+    to, NaN for every other lane."""
+    valid = st == (ENDED if N_eval is None else TARGET)
+    out[:, run] = np.where(valid[None, :], got, np.nan)
+    n_end[run] = np.where(st == ENDED, ends, np.nan)
+    status[run] = st
 
 
 def power_spectra(artifact: CompilationArtifact, pars, N_exit, fields_init, derivatives_init, *, N_eval=None, N_sub: float = 5.0, max_steps: int = 1_000_000,
@@ -846,7 +863,11 @@ def power_spectra(artifact: CompilationArtifact, pars, N_exit, fields_init, deri
     ``NONFINITE``.  The kernels are built into ``<artefact>.modes`` on first use (``CompilationArtifact.ensure_modes``).  Bad
     arguments raise before anything runs on the device."""
     args = _check_spectra(artifact, pars, N_exit, fields_init, derivatives_init, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
-    out, h_exit, n_exit, lane_start, n_end, status = _mode_lanes(artifact, False, *args)
+    return _power_spectra_result(*_mode_lanes(artifact, False, *args))
+
+
+def _power_spectra_result(out, h_exit, n_exit, lane_start, n_end, status) -> PowerSpectra:
+    """:class:`PowerSpectra` from what ``_mode_lanes`` returns"""
     B, K = h_exit.shape
     out = out.reshape(22, B, K)
     offset = lane_start.reshape(B, K)
@@ -885,6 +906,161 @@ def spectrum_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: i
         status[run] = ps.status[:, 0]
     spectra, status = spectra.reshape(3, N0, N1), status.reshape(N0, N1)
     return (tuple(spectra), state, n_end, status) if return_status else (tuple(spectra), state, n_end)
+
+
+class SpectraEvolution(NamedTuple):
+    """What :func:`spectra_evolution` returns, for B trajectories, K wavenumbers and S samples.  ``P_R``, ``P_S``, ``C_RS`` and
+    ``eps_H`` (B, K, S): the spectra of :class:`PowerSpectra` and epsilon_H at every sample; ``N`` (B, K, S): the e-fold count of the
+    sample since the trajectory's start -- the sample itself with ``since="start"``, ``N_exit[j]`` plus it with ``since="exit"`` --
+    where the lane emitted it; ``k`` (B, K) as in :class:`PowerSpectra`; ``end``: the :class:`PowerSpectra` that ``power_spectra``
+    returns for the same arguments, bit for bit (all NaN for a run of samples alone); ``status`` (B, K) int8, ``end.status``.
+
+    A sample a lane never reached is NaN in all five arrays: one before the mode's start, one after the point where the lane
+    stopped, every sample of a lane whose stage 1 found no start state.  UNLIKE ``end``, whose values are NaN unless the lane stopped
+    where it was asked to, the samples of a lane are kept up to where it stopped WHATEVER its status: a lane whose steps ran out
+    (``COMPLETE``) or whose step control failed still returns the samples it passed, and ``status`` tells."""
+
+    P_R: np.ndarray
+    P_S: np.ndarray
+    C_RS: np.ndarray
+    N: np.ndarray
+    eps_H: np.ndarray
+    k: np.ndarray
+    end: PowerSpectra
+    status: np.ndarray
+
+
+def _check_evolution_samples(samples, since, n_exit, N_eval, N_sub):
+    """(samples (S,), shift (K,)): the checked sample list of ``spectra_evolution`` and what a lane of wavenumber j subtracts from it"""
+    if since not in ("exit", "start"):
+        raise ValueError(f"since must be 'exit' or 'start' (got {since!r})")
+    try:
+        samples = np.ascontiguousarray(samples, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("samples must be convertible to a float64 array") from None
+    if samples.ndim != 1:
+        raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+    if samples.size < 1 or samples.size >= 2**32:
+        raise ValueError("samples must hold at least one e-fold count (and fewer than 2^32)")
+    if not (np.isfinite(samples).all() and (np.diff(samples) > 0.0).all()):
+        raise ValueError("samples must be finite and strictly increasing")
+    starts = n_exit - N_sub
+    if since == "exit":
+        if samples[0] < -N_sub:
+            raise ValueError(f"samples since the exit must be >= -N_sub = {-N_sub}: a mode starts N_sub e-folds before its exit (got {samples[0]})")
+        shift = np.full(n_exit.size, -N_sub)
+    else:
+        shift = starts
+    if N_eval is not None and not ((samples[-1] - shift) <= (N_eval - starts)).all():
+        raise ValueError(f"no sample may lie beyond N_eval = {N_eval} (the last one is {samples[-1]}, since={since!r})")
+    return samples, shift
+
+
+def spectra_evolution(artifact: CompilationArtifact, pars, N_exit, samples, fields_init, derivatives_init, *, since: str = "exit", N_eval=None,
+                      N_sub: float = 5.0, max_steps: int = 1_000_000, max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None,
+                      stop_at_end: bool = True) -> SpectraEvolution:  # fmt: skip
+    """``power_spectra`` with the spectra of every mode sampled along its evolution: P_R, P_S, C_RS and epsilon_H of the B K lanes at
+    the S e-fold counts ``samples`` as well as where the lanes stop, from ONE integration of every lane (csrc/inflx_evolution.h) --
+    how a mode's curvature power grows after horizon exit while the trajectory turns, and how its isocurvature power decays.  Every
+    argument of ``power_spectra`` means what it means there, and both stages are its own.
+
+    ``samples`` (S,), finite and strictly increasing, shared by all lanes.  ``since="exit"``: e-folds since each mode's own horizon
+    exit, each >= ``-N_sub`` (a negative one lies inside the horizon); the lane of wavenumber j is sampled at ``N_exit[j] + samples``
+    since the trajectory's start.  ``since="start"``: e-fold counts since the trajectory's start; a sample before a mode's start,
+    ``N_exit[j] - N_sub``, comes back NaN for that mode, and a sample exactly there is the vacuum, P_R = P_S = kappa^2 / (8 pi^2 eps),
+    C_RS = 0.  ``N_eval=None`` with ``stop_at_end=False`` is allowed here: the lanes stop at their last sample and ``end`` is NaN.  With
+    ``N_eval`` given no sample may lie beyond it.
+
+    A lane steps from the end state of each accepted step, never from a located state, so its steps are those of ``power_spectra``'s
+    lane: ``end`` is ``power_spectra``'s result bit for bit, and with ``since="start"`` the values at a sample are those of
+    ``power_spectra(N_eval=sample)`` bit for bit -- located with the same dense output, epsilon_H from the model at the located
+    state.  The step that ends inflation emits the samples up to N_end only.  See :class:`SpectraEvolution` for what a lane that did
+    not stop where asked returns.  The kernels are built into ``<artefact>.evolution`` on first use
+    (``CompilationArtifact.ensure_evolution``); the modes object is not needed.  Bad arguments raise before anything runs on the
+    device."""
+    args = _check_spectra(artifact, pars, N_exit, fields_init, derivatives_init, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end or N_eval is None)
+    p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, _ = args
+    stop_at_end = bool(stop_at_end)
+    samples, shift = _check_evolution_samples(samples, since, n_exit, N_eval, N_sub)
+    B, K, S = x.shape[0], n_exit.size, samples.size
+    h_exit, status, run, lane_start, lane_p, init, kappa, target = _mode_stage1(artifact, p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
+    out = np.full((22, B * K), np.nan)
+    n_end = np.full(B * K, np.nan)
+    sampled = np.full((S, _native.EV_SAMPLE_PLANES, B * K), np.nan)
+    if run.size:
+        artifact.ensure_evolution()
+        lib = _dylib(artifact, background=False)
+        got, sm, ends, st = lib.mode_evolution(lane_p, init, kappa, target, np.ascontiguousarray(np.tile(shift, B)[run]), samples, max_steps, _METHODS[solver],
+                                               max_err, dt or 0.0, _native.EOM_STOP_AT_END if stop_at_end else 0)  # fmt: skip
+        _mode_stage2_result(out, n_end, status, run, N_eval, got, ends, st)
+        sampled[:, :, run] = sm
+    end = _power_spectra_result(out, h_exit, n_exit, lane_start, n_end, status)
+    return _evolution_result(sampled, samples, since, n_exit, end)
+
+
+def _evolution_result(sampled, samples, since, n_exit, end: PowerSpectra) -> SpectraEvolution:
+    """:class:`SpectraEvolution` from the sample planes (S, 6, B K) and ``end``"""
+    B, K = end.k.shape
+    planes = np.moveaxis(sampled, 0, 2).reshape(sampled.shape[1], B, K, samples.size)  # [plane][b][j][sample]
+    where = samples[None, None, :] + (n_exit[None, :, None] if since == "exit" else 0.0)
+    n = np.where(np.isnan(planes[3]), np.nan, np.broadcast_to(where, planes[3].shape))
+    return SpectraEvolution(planes[0], planes[1], planes[2], n, planes[5], end.k, end, end.status)
+
+
+def evolution_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, samples, N_star: float = 55.0, N_sub: float = 5.0,
+                  derivatives_init=(0.0, 0.0), max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """``horizon_exit_map`` with ``N_star + N_sub`` (otherwise the same arguments) followed by ``spectra_evolution(N_exit=[N_sub],
+    since="exit")`` from every state found to the end of inflation, with ``spectrum_map``'s conventions: ``((P_R, P_S, C_RS), state,
+    N_end)`` with the three (N0, N1, S) spectra, at ``samples`` e-folds after its horizon exit, of the mode that leaves the horizon
+    ``N_star`` e-folds before the end of inflation, from the trajectory of every grid point; ``state`` and ``N_end`` exactly
+    ``horizon_exit_map``'s at ``N_star + N_sub``.  NaN where no such state was found and at a sample the second stage did not reach;
+    ``return_status=True`` adds the (N0, N1) status map as ``spectrum_map`` does."""
+    N_sub = _check_n_sub(N_sub)
+    try:
+        N_star = float(N_star)
+    except (TypeError, ValueError):
+        raise ValueError("N_star must be a number") from None
+    if not (math.isfinite(N_star) and N_star >= 0.0):
+        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    samples, _ = _check_evolution_samples(samples, "exit", np.array([N_sub]), None, N_sub)
+    state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star + N_sub, derivatives_init, max_steps, max_err, solver, return_status=True)
+    N0, N1 = n_end.shape
+    flat = state.reshape(-1, 5)
+    status = status.copy().reshape(-1)
+    spectra = np.full((3, N0 * N1, samples.size), np.nan)
+    run = np.flatnonzero(status == TARGET)
+    if run.size:
+        ev = spectra_evolution(artifact, pars, [N_sub], samples, flat[run, :2], flat[run, 2:4], since="exit", N_sub=N_sub, max_steps=max_steps, max_err=max_err,
+                               solver=solver)  # fmt: skip
+        spectra[:, run] = ev.P_R[:, 0], ev.P_S[:, 0], ev.C_RS[:, 0]
+        status[run] = ev.status[:, 0]
+    spectra, status = spectra.reshape(3, N0, N1, samples.size), status.reshape(N0, N1)
+    return (tuple(spectra), state, n_end, status) if return_status else (tuple(spectra), state, n_end)
+
+
+def transfer_from_spectra(ev, ref: int):
+    """The transfer functions that the sampled spectra ``ev`` (:class:`SpectraEvolution`, or anything with ``P_R``, ``P_S`` and
+    ``C_RS`` of shape (..., S)) imply between the sample of index ``ref`` -- taken after horizon exit, marked * -- and every sample:
+    with R = R* + T_RS S* and S = T_SS S*,
+
+        T_SS = sqrt(P_S / P_S*),      T_RS = (C_RS / T_SS - C_RS*) / P_S*,
+
+    and the residual P_R - (P_R* + 2 T_RS C_RS* + T_RS^2 P_S*) of the third relation, which the two do not use: how far the evolution
+    between the two samples is from that super-horizon form.  Returns ``(T_RS, T_SS, residual)``, each of the spectra's shape; at
+    ``ref`` itself T_SS = 1, T_RS = 0 and the residual is 0.  A pure function of its arguments: the measured counterpart of
+    ``transfer_functions``' T_RS and T_SS, in the same orientation of e_s."""
+    ref = operator.index(ref)
+    p_r, p_s, c_rs = (np.asarray(a, dtype=np.float64) for a in (ev.P_R, ev.P_S, ev.C_RS))
+    if not (p_r.shape == p_s.shape == c_rs.shape and p_r.ndim >= 1):
+        raise InflatoxShapeError(f"P_R, P_S and C_RS must have one shape (..., S) (got {p_r.shape}, {p_s.shape} and {c_rs.shape})")
+    if not -p_r.shape[-1] <= ref < p_r.shape[-1]:
+        raise ValueError(f"ref must index one of the {p_r.shape[-1]} samples (got {ref})")
+    r0, s0, c0 = p_r[..., ref, None], p_s[..., ref, None], c_rs[..., ref, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t_ss = np.sqrt(p_s / s0)
+        t_rs = (c_rs / t_ss - c0) / s0
+        residual = p_r - (r0 + 2.0 * t_rs * c0 + t_rs * t_rs * s0)
+    return t_rs, t_ss, residual
 
 
 class TensorSpectra(NamedTuple):

@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -384,6 +384,20 @@ class CompilationArtifact:
         of them is involved."""
         return self._ensure_companion("deltan", _DELTAN_SOURCES, "dn{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "dn{key}.eom.h", self.eom_header_text())])
 
+    def ensure_evolution(self) -> str:
+        """Extension: build the evolution code object of this model -- the kernels of ``inflatox_amd.background.spectra_evolution``
+        (csrc/inflx_evolution_kernels.hip) -- and return its path, ``shared_object_path + ".evolution"``, where ``libinflx_hip.so``
+        looks for it.  One hipcc step on first use from the core object's header and options, the header of the equations of motion,
+        the kinematics header and the masses header, cached as ``<tag>.ev<hash>.hsaco`` (the hash covers the three generated headers
+        and ``_EVOLUTION_SOURCES``, code only -- csrc/inflx_modes.h and csrc/inflx_background.h among them, whose lane the kernels
+        run); the object carries the core object's ``MODEL_TAG`` and a layout word of its own (``INFLX_EV_ABI``).  Like the other
+        seven companion objects it lies outside the kernel groups, and none of them is involved: not the modes object either."""
+        return self._ensure_companion(
+            "evolution", _EVOLUTION_SOURCES, "ev{key}.hsaco",
+            lambda: [("INFLX_EOM_HEADER", "ev{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "ev{key}.kin.h", self.kinematics_header_text()),
+                     ("INFLX_MASS_HEADER", "ev{key}.mass.h", self.masses_header_text())],
+        )  # fmt: skip
+
     def ensure_rowpass(self) -> str | None:
         """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
         evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
@@ -511,6 +525,8 @@ _TRANSFER_SOURCES = ("inflx_transfer_kernels.hip", "inflx_transfer.h", "inflx_tr
 _MODES_SOURCES = ("inflx_modes_kernels.hip", "inflx_modes.h", "inflx_modes_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _TENSOR_SOURCES = ("inflx_tensor_kernels.hip", "inflx_tensor.h", "inflx_tensor_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _DELTAN_SOURCES = ("inflx_deltan_kernels.hip", "inflx_deltan.h", "inflx_deltan_abi.h", "inflx_background.h", "inflx_background_abi.h")
+_EVOLUTION_SOURCES = ("inflx_evolution_kernels.hip", "inflx_evolution.h", "inflx_evolution_abi.h", "inflx_modes.h", "inflx_modes_abi.h", "inflx_background.h",
+                      "inflx_background_abi.h")  # fmt: skip
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 

@@ -49,6 +49,7 @@
 #include "inflx_modes_abi.h"
 #include "inflx_tensor_abi.h"
 #include "inflx_deltan_abi.h"
+#include "inflx_evolution_abi.h"
 
 namespace {
 
@@ -369,7 +370,7 @@ struct TableRing {
 
 // The code objects beside the core object that the background solver's families live in (kCompanions describes them), and what a
 // handle holds of one: its module and its kernels, in the order of the description's names.
-enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kCompanionCount };
+enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kCompanionCount };
 constexpr int kCompanionKernels = 10;  // the most kernels of one object (background)
 struct CompanionSlot {
   hipModule_t module = nullptr;
@@ -2891,7 +2892,7 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* mm, int op, const double* p, siz
 }  // extern "C"
 
 // ---- the background solver: what its families share ---------------------------------------------------------------------------
-// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N -- has its kernels in
+// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution -- has its kernels in
 // a code object of its own beside the core object, `<artefact>.<suffix>`, which CompilationArtifact.ensure_<suffix>() builds.
 // kCompanions has one constant description per object: the words of its messages, its layout word, its kernels.  need_companion
 // loads any of them into its slot of the handle on first use, and a call site names a kernel by its family's index below.  The
@@ -2908,6 +2909,7 @@ static_assert(kAbiMajor == INFLX_TR_DEFAULT_ABI_MAJOR, "a transfer object report
 static_assert(kAbiMajor == INFLX_MD_DEFAULT_ABI_MAJOR, "a modes object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_TN_DEFAULT_ABI_MAJOR, "a tensor object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_DN_DEFAULT_ABI_MAJOR, "a delta-N object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_EV_DEFAULT_ABI_MAJOR, "an evolution object reports the core object's ABI major: change both together");
 
 struct CompanionDesc {
   const char* suffix;      // the file is `<artefact>.<suffix>` and CompilationArtifact.ensure_<suffix>() builds it
@@ -2921,7 +2923,7 @@ struct CompanionDesc {
 // the kernels of an object, by their place in its description; `+ method` is + 0 for INFLX_EOM_RK4 and + 1 for INFLX_EOM_RKF
 enum BgKernel { kBgInit, kBgRowsTranspose, kBgAdvance /* + 2 method + store rows */, kBgTarget = 6 /* + method */, kBgSampled = 8 /* + method */ };
 enum StateKernel { kStates };                                // kinematics, masses
-enum LaneKernel { kLaneInit, kLaneAdvance /* + method */ };  // transfer, modes, tensor
+enum LaneKernel { kLaneInit, kLaneAdvance /* + method */ };  // transfer, modes, tensor, evolution
 enum DnKernel { kDnInit, kDnReduce, kDnEnd /* + method: phase A */, kDnSurface = 4 /* + method: phase B */ };
 const CompanionDesc kCompanions[kCompanionCount] = {
     {"background", "background kernels", "are", "inflatox_amd.background", "INFLX_BG_ABI", INFLX_BG_ABI_VERSION,
@@ -2937,6 +2939,8 @@ const CompanionDesc kCompanions[kCompanionCount] = {
      {"inflx_tn_init", "inflx_tn_advance_rk4", "inflx_tn_advance_rkf"}},
     {"deltan", "delta-N kernels", "are", "inflatox_amd.background.delta_N", "INFLX_DN_ABI", INFLX_DN_ABI_VERSION,
      {"inflx_dn_init", "inflx_dn_reduce", "inflx_dn_end_rk4", "inflx_dn_end_rkf", "inflx_dn_surface_rk4", "inflx_dn_surface_rkf"}},
+    {"evolution", "evolution kernels", "are", "inflatox_amd.background.spectra_evolution", "INFLX_EV_ABI", INFLX_EV_ABI_VERSION,
+     {"inflx_ev_init", "inflx_ev_advance_rk4", "inflx_ev_advance_rkf"}},
 };
 
 // Load the companion object `which` beside the core object, unless the handle has it: it must carry the core object's VERSION and
@@ -3006,12 +3010,13 @@ int check_integrator_args(const inflx_model* m, const char* phrase, const char* 
   return check_integrator_args(m, phrase, noun, p, P, n_p, B, method, flags, known_flags, [] { return (int)INFLX_OK; }, max_steps, max_err, dt, status);
 }
 
-// the list of S samples all lanes of a call share: finite, >= 0, strictly increasing
-int check_samples(const double* samples, size_t S) {
+// the list of S samples all lanes of a call share: finite, >= 0 (unless `negative`: a lane's own shift moves them), strictly increasing
+int check_samples(const double* samples, size_t S, bool negative = false) {
   if (S < 1 || (uint64_t)S > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of samples must be in [1, 2^32) (got %zu)", S);
   if (!samples) return fail(INFLX_ERR_ARG, "sample array is NULL");
   for (size_t k = 0; k < S; ++k) {
-    if (!std::isfinite(samples[k]) || samples[k] < 0.0) return fail(INFLX_ERR_ARG, "sample %zu is not a finite number >= 0", k);
+    if (!std::isfinite(samples[k])) return fail(INFLX_ERR_ARG, negative ? "sample %zu is not a finite number" : "sample %zu is not a finite number >= 0", k);
+    if (!negative && samples[k] < 0.0) return fail(INFLX_ERR_ARG, "sample %zu is not a finite number >= 0", k);
     if (k && !(samples[k] > samples[k - 1])) return fail(INFLX_ERR_ARG, "samples must be strictly increasing (sample %zu is not above sample %zu)", k, k - 1);
   }
   return INFLX_OK;
@@ -3598,30 +3603,50 @@ int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n
 // ---- mode functions and power spectra (inflx_mode_spectra) ------------------------------------------------------------------------
 namespace {
 
-// the layouts of the two kinds of lane inflx_mode_spectra runs (csrc/inflx_modes_abi.h, csrc/inflx_tensor_abi.h), and their objects
+// the layouts of the two kinds of lane inflx_mode_spectra runs (csrc/inflx_modes_abi.h, csrc/inflx_tensor_abi.h) and of
+// inflx_mode_evolution's (csrc/inflx_evolution_abi.h), and their objects; kSamplePlanes: what a lane returns per sample
 struct MdLayout {
   using Args = InflxMdArgs;
   static constexpr Companion kObject = kObjModes;
+  static constexpr size_t kSamplePlanes = 0;
   static constexpr size_t kThreads = INFLX_MD_THREADS, kOutPlanes = INFLX_MD_OUT_PLANES, kCarryPlanes = INFLX_MD_CARRY_PLANES, kCarryNend = INFLX_MD_CARRY_NEND,
                           kCarryStatus = INFLX_MD_CARRY_STATUS;
 };
 struct TnLayout {
   using Args = InflxTnArgs;
   static constexpr Companion kObject = kObjTensor;
+  static constexpr size_t kSamplePlanes = 0;
   static constexpr size_t kThreads = INFLX_TN_THREADS, kOutPlanes = INFLX_TN_OUT_PLANES, kCarryPlanes = INFLX_TN_CARRY_PLANES, kCarryNend = INFLX_TN_CARRY_NEND,
                           kCarryStatus = INFLX_TN_CARRY_STATUS;
 };
+struct EvLayout {
+  using Args = InflxEvArgs;
+  static constexpr Companion kObject = kObjEvolution;
+  static constexpr size_t kSamplePlanes = INFLX_EV_SAMPLE_PLANES;
+  static constexpr size_t kThreads = INFLX_EV_THREADS, kOutPlanes = INFLX_EV_OUT_PLANES, kCarryPlanes = INFLX_EV_CARRY_PLANES, kCarryNend = INFLX_EV_CARRY_NEND,
+                          kCarryStatus = INFLX_EV_CARRY_STATUS;
+};
+// the samples of an EvLayout call: the per-lane shift (B,), the shared list (S,) and the host result (S, kSamplePlanes, B)
+struct LaneSamples {
+  const double* shift;
+  const double* samples;
+  size_t S;
+  double* sampled;
+};
 
-// inflx_mode_spectra over lanes of layout L, its arguments checked: the object of L, then the passes, launches and read-back.
+// inflx_mode_spectra and inflx_mode_evolution over lanes of layout L, their arguments checked: the object of L, then the passes,
+// launches and read-back.  `sm`: the samples of an EvLayout call -- every statement about them stands under L::kSamplePlanes, so the
+// other two layouts make the calls they made without it, in their order.
 template <class L>
 int run_mode_lanes(inflx_model* m, int method, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* kappa, const double* n_target,
-                   size_t max_steps, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status) {
+                   size_t max_steps, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status, const LaneSamples* sm = nullptr) {
   int rc = need_companion(m, L::kObject);
   if (rc) return rc;
   const CompanionSlot& obj = m->companion[L::kObject];
   hipFunction_t advance = obj.fn[kLaneAdvance + (method == INFLX_EOM_RKF ? 1 : 0)];
   hipStream_t s = m->stream;
-  const size_t nc_max = inflx_bg_lanes_per_pass(B, L::kOutPlanes * sizeof(double), L::kThreads);
+  const size_t sample_planes = L::kSamplePlanes ? L::kSamplePlanes * sm->S : 0;  // per lane, all samples
+  const size_t nc_max = inflx_bg_lanes_per_pass(B, (L::kOutPlanes + sample_planes) * sizeof(double), L::kThreads);
   constexpr size_t kBack = L::kCarryPlanes - L::kCarryNend;  // the carry planes read back: NEND, STATUS
   DeviceBuffers dev;
   double *d_p = nullptr, *d_init = nullptr, *d_kappa = nullptr, *d_target = nullptr, *d_carry = nullptr, *d_out = nullptr;
@@ -3629,6 +3654,11 @@ int run_mode_lanes(inflx_model* m, int method, const double* p, size_t P, size_t
   if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_kappa, nc_max)) || (rc = dev.array(&d_target, nc_max)) ||
       (rc = dev.array(&d_carry, nc_max * L::kCarryPlanes)) || (rc = dev.array(&d_out, nc_max * L::kOutPlanes)) || (rc = dev.array(&d_running, 1)))
     return rc;
+  double *d_shift = nullptr, *d_samples = nullptr, *d_sampled = nullptr;
+  if constexpr (L::kSamplePlanes != 0) {
+    if ((rc = dev.array(&d_shift, nc_max)) || (rc = dev.array(&d_samples, sm->S)) || (rc = dev.array(&d_sampled, nc_max * sample_planes))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_samples, sm->samples, sm->S * sizeof(double), hipMemcpyHostToDevice, s));
+  }
   std::vector<double> host_carry(nc_max * kBack);
 
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
@@ -3647,6 +3677,14 @@ int run_mode_lanes(inflx_model* m, int method, const double* p, size_t P, size_t
     a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
     a.max_err = max_err;
     a.fixed_dt = dt;
+    if constexpr (L::kSamplePlanes != 0) {
+      a.shift = d_shift;
+      a.samples = d_samples;
+      a.sampled = d_sampled;
+      a.n_samples = (uint32_t)sm->S;
+      HIP_TRY(hipMemcpyAsync(d_shift, sm->shift + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemsetAsync(d_sampled, 0xff, n * sample_planes * sizeof(double), s));
+    }
     void* params[] = {&a};
     const unsigned grid = (unsigned)((n + L::kThreads - 1) / L::kThreads);
     HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -3658,6 +3696,8 @@ int run_mode_lanes(inflx_model* m, int method, const double* p, size_t P, size_t
     if ((rc = advance_until_done(advance, a, grid, L::kThreads, max_steps, s))) return rc;
     // the planes as they are: a plane of this pass's lanes is n doubles, B doubles apart in `out`
     HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), d_out, n * sizeof(double), n * sizeof(double), L::kOutPlanes, hipMemcpyDeviceToHost, s));
+    if constexpr (L::kSamplePlanes != 0)  // ... and the S x 6 sample planes likewise
+      HIP_TRY(hipMemcpy2DAsync(sm->sampled + c0, B * sizeof(double), d_sampled, n * sizeof(double), n * sizeof(double), sample_planes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry + (size_t)L::kCarryNend * n, n * kBack * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const double* hc = host_carry.data();
@@ -3687,6 +3727,32 @@ int inflx_mode_spectra(inflx_model* m, const double* p, size_t P, size_t n_p, co
   HIP_TRY(hipSetDevice(m->device));
   if (flags & INFLX_MODES_TENSOR) return run_mode_lanes<TnLayout>(m, method, p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
   return run_mode_lanes<MdLayout>(m, method, p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status);
+}
+
+}  // extern "C"
+
+// ---- spectra of a mode sampled along its evolution (inflx_mode_evolution) -----------------------------------------------------------
+extern "C" {
+
+int inflx_mode_evolution(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* kappa, const double* n_target,
+                         const double* shift, const double* samples, size_t S, size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out,
+                         double* sampled, double* efolds, int8_t* status) {
+  INFLX_SERIALISE(m);
+  int rc = check_integrator_args(m, "the mode functions require", "lane", p, P, n_p, B, method, flags, INFLX_EOM_STOP_AT_END, max_steps, max_err, dt, status);
+  if (rc) return rc;
+  if ((rc = check_samples(samples, S, true))) return rc;
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  if (!kappa) return fail(INFLX_ERR_ARG, "kappa array is NULL");
+  if (!n_target) return fail(INFLX_ERR_ARG, "n_target array is NULL");
+  if (!shift) return fail(INFLX_ERR_ARG, "shift array is NULL");
+  if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
+  if (!sampled) return fail(INFLX_ERR_ARG, "sample output array is NULL");
+  for (size_t b = 0; b < B; ++b)
+    if (!std::isfinite(shift[b])) return fail(INFLX_ERR_ARG, "shift %zu is not a finite number", b);
+  HIP_TRY(hipSetDevice(m->device));
+  const LaneSamples sm{shift, samples, S, sampled};
+  return run_mode_lanes<EvLayout>(m, method, p, P, n_p, init, B, kappa, n_target, max_steps, max_err, dt, flags, out, efolds, status, &sm);
 }
 
 }  // extern "C"
