@@ -674,5 +674,7 @@ int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p
 #include "inflx_hip_deltan.h"
 /* the spectra of a mode sampled along its evolution (inflx_mode_spectra with samples): likewise */
 #include "inflx_hip_evolution.h"
+/* stochastic e-folds (Langevin noise on every trajectory, moments of N over the realisations): likewise */
+#include "inflx_hip_stochastic.h"
 
 #endif /* INFLX_HIP_H */

@@ -149,6 +149,17 @@ EVOLUTION_SIGNATURES = {
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _DP, _DP, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, _DP, C.POINTER(C.c_int8)],
     ),
 }
+# ... and for include/inflx_hip_stochastic.h
+STOCHASTIC_SIGNATURES = {
+    "inflx_stochastic_efolds": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, C.POINTER(C.c_uint32), C.c_uint64, C.c_double, C.c_double, C.c_double, _SIZE, C.c_int, C.c_double, C.c_double,
+         _DP, _DP],
+    ),
+}
+ST_OUT_PLANES = 12  # mean, m2, m3, m4, min, max, lanes per status 0..5
+ST_SAMPLE_PLANES = 7  # N, phi^0, phi^1, chi^0, chi^1, H, status
+ST_MAX_REALISATIONS = 1 << 20
 EV_SAMPLE_PLANES = 6
 DN_FIXED, DN_SLOW_ROLL, DN_EXPLICIT = 0, 1, 2  # inflx_dn_velocity
 DN_LOCATED, DN_PAST_SURFACE = 7, 8  # inflx_dn_status
@@ -166,7 +177,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h"), os.path.join(_PKG, "csrc", "inflx_stochastic_abi.h"), os.path.join(_REPO, "include", "inflx_hip_stochastic.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -222,7 +233,7 @@ def load_library():
             )
         _preload_hip_runtime()
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items(), *EVOLUTION_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items(), *EVOLUTION_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -745,6 +756,33 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return out, surface, status
+
+    # ---- stochastic e-folds (include/inflx_hip_stochastic.h: inflx_stochastic_efolds) --------------
+    def stochastic_efolds(self, p, init, R: int, streams, seed: int, noise_scale: float, dn_max: float, n_stop: float, max_steps: int, method: int,
+                          max_err: float, dt: float, want_samples: bool = False):
+        """B points from ``init`` (B,4), ``R`` realisations of the Langevin equation each; ``streams`` (B,) uint32 or None (the
+        point's index); ``n_stop`` NaN for none.  Returns (moments (12, B): mean, m2, m3, m4, min, max of N_end over the lanes that
+        ended inflation and the lanes per status 0..5, point fastest; samples (7, B * R): N, phi^0, phi^1, chi^0, chi^1, H, status,
+        lane b * R + r fastest -- or None).  The stochastic object must be in place (``CompilationArtifact.ensure_stochastic``)."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        B = init.shape[0]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint32)
+            if streams.shape != (B,):
+                raise InflatoxShapeError(f"streams must have shape ({B},) (got {streams.shape})")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        moments = np.empty((ST_OUT_PLANES, B))
+        samples = np.empty((ST_SAMPLE_PLANES, B * int(R))) if want_samples else None
+        _check(
+            self._lib.inflx_stochastic_efolds(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(R), None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint32)),
+                int(seed), float(noise_scale), float(dn_max), float(n_stop), int(max_steps), int(method), float(max_err), float(dt), _ptr(moments),
+                None if samples is None else _ptr(samples),
+            )
+        )  # fmt: skip
+        return moments, samples
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

@@ -28,6 +28,9 @@ own -- the scalar tilt n_s, its running, the tensor tilt n_t and the tensor-to-s
 ``horizon_exit_map`` followed by it.  ``spectra_evolution`` is ``power_spectra`` with every mode's spectra sampled at a list of e-fold counts
 along its evolution, from one integration of every lane; ``evolution_map`` is ``horizon_exit_map`` followed by it, and
 ``transfer_from_spectra`` reads the transfer functions T_RS and T_SS off such samples: the measured counterpart of ``transfer_functions``.
+``stochastic_efolds`` adds the Langevin noise of the separate-universe picture to every trajectory -- a field kick of variance (H / 2 pi)^2
+per e-fold, right on a curved field space -- and returns the moments of the e-fold count over many realisations of every point, the
+input of the stochastic delta-N formalism; ``stochastic_map`` places the points on a sweep grid.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -54,7 +57,8 @@ from .compiler import CompilationArtifact
 __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map", "state_at_efolds", "horizon_exit_map", "solve_eom_sampled", "EoMSolution", "EfoldsState",
            "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses", "transfer_functions", "transfer_map",
            "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra", "tensor_spectra", "TensorSpectra", "observables", "Observables", "observables_map",
-           "delta_N", "DeltaN", "fnl_map", "delta_N_status", "spectra_evolution", "SpectraEvolution", "evolution_map", "transfer_from_spectra"]  # fmt: skip
+           "delta_N", "DeltaN", "fnl_map", "delta_N_status", "spectra_evolution", "SpectraEvolution", "evolution_map", "transfer_from_spectra",
+           "stochastic_efolds", "stochastic_map", "StochasticEfolds"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -1399,3 +1403,157 @@ def fnl_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N
     status = status.reshape(N0, N1)
     dn = DeltaN(*(values[name].reshape(N0, N1, *shapes.get(name, ())) for name in DeltaN._fields[:-1]), status)
     return (dn, state, n_end, status) if return_status else (dn, state, n_end)
+
+
+class StochasticEfolds(NamedTuple):
+    """What :func:`stochastic_efolds` returns, every member (B,) unless noted (``stochastic_map``: (N0, N1) in place of (B,)).
+    ``N_mean``, ``N_var``, ``N_m3``, ``N_m4``: the mean and the central moments sum (N - mean)^k / n_ended, k = 2, 3, 4, of the e-fold
+    count at the end of inflation, ``N_min`` and ``N_max`` its extremes -- all over the realisations that ENDED inflation, NaN where
+    none did; ``n_ended`` their number; ``counts`` (B, 6): the realisations per ``STATUS`` code 0..5; ``N_classical``: the e-fold count
+    of the trajectory without noise (NaN where it did not end).  With ``return_samples``, else None: ``N`` (B, R), N_end of a
+    realisation that ended inflation and the e-fold count where it stopped otherwise; ``state`` (B, R, 5): phi^0, phi^1, chi^0, chi^1,
+    H there; ``status`` (B, R) int8."""
+
+    N_mean: np.ndarray
+    N_var: np.ndarray
+    N_m3: np.ndarray
+    N_m4: np.ndarray
+    N_min: np.ndarray
+    N_max: np.ndarray
+    n_ended: np.ndarray
+    counts: np.ndarray
+    N_classical: np.ndarray
+    N: np.ndarray | None = None
+    state: np.ndarray | None = None
+    status: np.ndarray | None = None
+
+
+def _check_stochastic_options(artifact, realisations, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt):
+    """The checks ``stochastic_efolds`` and ``stochastic_map`` share: (R, seed, noise_scale, dN_max, N_stop (NaN: none), max_steps,
+    max_err, dt)."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    try:
+        R = operator.index(realisations)
+        seed = operator.index(seed)
+    except TypeError:
+        raise ValueError("realisations and seed must be integers") from None
+    if R < 1 or R > _native.ST_MAX_REALISATIONS:
+        raise ValueError(f"realisations must be in [1, 2^20] (got {R})")
+    if seed < 0 or seed >= 2**64:
+        raise ValueError(f"seed must be in [0, 2^64) (got {seed})")
+    try:
+        noise_scale, dN_max = float(noise_scale), float(dN_max)
+        N_stop = math.nan if N_stop is None else float(N_stop)
+    except (TypeError, ValueError):
+        raise ValueError("noise_scale, dN_max and N_stop must be numbers") from None
+    if not (math.isfinite(noise_scale) and noise_scale >= 0.0):
+        raise ValueError(f"noise_scale must be finite and >= 0 (got {noise_scale})")
+    if not dN_max > 0.0:
+        raise ValueError(f"dN_max must be positive (got {dN_max})")
+    if not math.isnan(N_stop) and not (math.isfinite(N_stop) and N_stop > 0.0):
+        raise ValueError(f"N_stop must be None or a positive finite number (got {N_stop})")
+    return R, seed, noise_scale, dN_max, N_stop, max_steps, max_err, dt
+
+
+def _check_streams(streams, B):
+    if streams is None:
+        return None
+    try:
+        ids = np.asarray(streams)
+        if ids.dtype.kind not in "iu":
+            raise TypeError
+        if ids.size and (ids.min() < 0 or ids.max() >= 2**32):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("streams must be integers in [0, 2^32)") from None
+    if ids.shape != (B,):
+        raise InflatoxShapeError(f"streams must have shape ({B},) (got {ids.shape})")
+    return np.ascontiguousarray(ids, dtype=np.uint32)
+
+
+def _stochastic_result(moments, classical, samples, B, R) -> StochasticEfolds:
+    counts = moments[6:12].T.astype(np.int64)
+    n_classical = np.where(classical[7] == 1.0, classical[0], np.nan)
+    extra = (None, None, None)
+    if samples is not None:
+        lanes = samples.reshape(_native.ST_SAMPLE_PLANES, B, R)
+        extra = (lanes[0], np.moveaxis(lanes[1:6], 0, -1), lanes[6].astype(np.int8))
+    return StochasticEfolds(moments[0], moments[1], moments[2], moments[3], moments[4], moments[5], counts[:, ENDED], counts, n_classical, *extra)
+
+
+def _stochastic_run(artifact, p, init, R, ids, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt, return_samples) -> StochasticEfolds:
+    artifact.ensure_stochastic()
+    lib = _dylib(artifact, background=False)
+    method, B = _METHODS[solver], init.shape[0]
+    moments, samples = lib.stochastic_efolds(p, init, R, ids, seed, noise_scale, dN_max, N_stop, max_steps, method, max_err, dt or 0.0, return_samples)
+    # the classical trajectory: the same entry point with one realisation and no noise (moments: its N_end is the mean and the minimum)
+    classical, _ = lib.stochastic_efolds(p, init, 1, ids, seed, 0.0, dN_max, N_stop, max_steps, method, max_err, dt or 0.0)
+    return _stochastic_result(moments, classical, samples, B, R)
+
+
+def stochastic_efolds(artifact: CompilationArtifact, pars, fields_init, derivatives_init, realisations: int, *, seed: int = 0, streams=None,
+                      noise_scale: float = 1.0, dN_max: float = 1.0 / 32.0, N_stop: float | None = None, max_steps: int = 1_000_000, max_err: float = 1e-8,
+                      solver: str = "rkf", dt: float | None = None, return_samples: bool = False) -> StochasticEfolds:  # fmt: skip
+    """The e-fold count to the end of inflation as a random variable: ``realisations`` (R, at most 2^20) solutions of the
+    separate-universe Langevin equation from each of the B states ``fields_init``, ``derivatives_init`` (both (B, 2)), one GPU lane
+    each, and the moments of N_end over them.  ``pars`` is one row or (B, n): point b uses row b for all its realisations.
+
+    A realisation is the classical trajectory of ``solve_eom_batch(..., stop_at_end=True)`` whose fields take, after every accepted
+    step over dN e-folds, the kick  phi^a += s (H / 2 pi) sqrt(dN) e^a_alpha xi^alpha - s^2 (H / 2 pi)^2 dN G^bc Gamma^a_bc / 2  with
+    e e^T = G^-1, xi standard normal and s = ``noise_scale``: Brownian motion of variance (H / 2 pi)^2 per e-fold on the field
+    manifold (the second term is what makes the law independent of the chart), in the units of ``delta_N``'s P_zeta.  The velocities
+    are not kicked -- the momentum noise is neglected -- and H follows the change of the energy density.  Adaptive runs try no step
+    longer than ``dN_max`` e-folds (``math.inf`` lifts the bound); a fixed ``dt`` is taken as given.  A realisation ends (``ENDED``)
+    where epsilon_H reaches 1, in a step (N_end interpolated as ``efolds_map`` does) or by a kick.  With ``N_stop`` it stops after that
+    many e-folds instead (``TARGET``), the last kick covering what is left: the diffusion over a fixed number of e-folds.
+
+    The random numbers are Philox4x32-10 with the key ``seed`` and the counter (accepted-step index, realisation, stream): a
+    realisation depends on (seed, stream, r) alone -- not on the batch, on R, or on how the run is split into launches.  ``streams``
+    (B,) gives every point a 32-bit stream id; the default is the point's index, so two points of a batch never share their noise.
+
+    The moments are CONDITIONAL on the end of inflation: they are taken over the ``n_ended`` realisations with status ``ENDED``, and
+    they are biased -- towards short trajectories -- wherever ``n_ended < R``, for the realisations that ran out of ``max_steps`` or
+    failed are the long or the odd ones; ``counts`` says what became of all R.  ``return_samples`` adds every realisation's N, state and
+    status.  The kernels are csrc/inflx_stochastic_kernels.hip, built into ``<artefact>.stochastic`` on first use
+    (``CompilationArtifact.ensure_stochastic``).  Bad arguments raise before anything runs on the device.  Returns a
+    :class:`StochasticEfolds`."""
+    R, seed, noise_scale, dN_max, N_stop, max_steps, max_err, dt = _check_stochastic_options(artifact, realisations, seed, noise_scale, dN_max, N_stop, max_steps,
+                                                                                             max_err, solver, dt)  # fmt: skip
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    B = x.shape[0]
+    ids = _check_streams(streams, B)
+    p = _pars(artifact, pars, B)
+    return _stochastic_run(artifact, p, np.concatenate([x, v], axis=1), R, ids, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt, bool(return_samples))
+
+
+def stochastic_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, realisations: int, *, derivatives_init=(0.0, 0.0), seed: int = 0,
+                   noise_scale: float = 1.0, dN_max: float = 1.0 / 32.0, N_stop: float | None = None, max_steps: int = 1_000_000, max_err: float = 1e-8,
+                   solver: str = "rkf", dt: float | None = None) -> StochasticEfolds:  # fmt: skip
+    """``stochastic_efolds`` from every point of an (N0, N1) grid over ``start_stop`` (the sweeps' layout and coordinate rule,
+    ``grid_points``), all trajectories starting with the velocities ``derivatives_init``: the same result as (N0, N1) maps (``counts``
+    (N0, N1, 6)), the stream of a point its index in the flattened grid.  Beside ``GeneralisedAL.flag_quantum_dif`` over the same grid it
+    says what the diffusion does where that flag is set.  It never returns samples."""
+    options = _check_stochastic_options(artifact, realisations, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt)
+    ss = np.asarray(start_stop, dtype=np.float64)
+    if ss.size != 4:
+        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
+    N0, N1 = operator.index(N0), operator.index(N1)
+    if N0 < 1 or N1 < 1:
+        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
+    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
+    if d.size != 2:
+        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
+    p = _pars(artifact, pars, 1)
+    if p.ndim != 1:
+        raise InflatoxShapeError("stochastic_map takes one parameter row")
+    x0, x1 = grid_points(ss, N0, N1)
+    init = np.empty((N0 * N1, 4))
+    init[:, 0] = np.repeat(x0, N1)
+    init[:, 1] = np.tile(x1, N0)
+    init[:, 2:] = d
+    R, seed, noise_scale, dN_max, N_stop, max_steps, max_err, dt = options
+    flat = _stochastic_run(artifact, p, init, R, None, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt, False)
+    return StochasticEfolds(*(a.reshape(N0, N1, *a.shape[1:]) for a in flat[:9]))

@@ -37,7 +37,7 @@ import numpy as np
 import sympy
 from sympy.printing.c import C99CodePrinter
 
-from .staging import HIPInflatoxPrinter, emit_eom_header, emit_kinematics_header, emit_masses_header, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
+from .staging import HIPInflatoxPrinter, emit_eom_header, emit_kinematics_header, emit_masses_header, emit_noise_header, emit_stage_header  # noqa: F401  (HIPInflatoxPrinter re-exported)
 from .symbolic import InflationModel
 from .version import __abi_version__, __version__
 
@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" / "stochastic" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -280,6 +280,11 @@ class CompilationArtifact:
         """The generated header of the covariant Hesse matrix along a trajectory and the Ricci scalar
         (``staging.emit_masses_header``), with this artefact's parameter numbering and ``cse`` setting."""
         return self._trajectory_header_text(emit_masses_header)
+
+    def noise_header_text(self) -> str:
+        """The generated header of the stochastic kick's geometry (``staging.emit_noise_header``), with this artefact's parameter
+        numbering and ``cse`` setting."""
+        return self._trajectory_header_text(emit_noise_header)
 
     def _ensure_companion(self, what: str, sources: tuple, object_name: str, headers) -> str:
         """``shared_object_path + "." + what``, where ``libinflx_hip.so`` looks for the companion object ``what``: built on first use by
@@ -396,6 +401,19 @@ class CompilationArtifact:
             "evolution", _EVOLUTION_SOURCES, "ev{key}.hsaco",
             lambda: [("INFLX_EOM_HEADER", "ev{key}.eom.h", self.eom_header_text()), ("INFLX_KIN_HEADER", "ev{key}.kin.h", self.kinematics_header_text()),
                      ("INFLX_MASS_HEADER", "ev{key}.mass.h", self.masses_header_text())],
+        )  # fmt: skip
+
+    def ensure_stochastic(self) -> str:
+        """Extension: build the stochastic code object of this model -- the kernels of ``inflatox_amd.background.stochastic_efolds``
+        (csrc/inflx_stochastic_kernels.hip) -- and return its path, ``shared_object_path + ".stochastic"``, where ``libinflx_hip.so``
+        looks for it.  One hipcc step on first use from the core object's header and options, the header of the equations of motion
+        and the noise header (``staging.emit_noise_header``), cached as ``<tag>.st<hash>.hsaco`` (the hash covers the two generated
+        headers and ``_STOCHASTIC_SOURCES``, code only -- csrc/inflx_background.h among them, whose stepper the kernels run); the
+        object carries the core object's ``MODEL_TAG`` and a layout word of its own (``INFLX_ST_ABI``).  Like the other eight
+        companion objects it lies outside the kernel groups, and none of them is involved."""
+        return self._ensure_companion(
+            "stochastic", _STOCHASTIC_SOURCES, "st{key}.hsaco",
+            lambda: [("INFLX_EOM_HEADER", "st{key}.eom.h", self.eom_header_text()), ("INFLX_NOISE_HEADER", "st{key}.noise.h", self.noise_header_text())],
         )  # fmt: skip
 
     def ensure_rowpass(self) -> str | None:
@@ -527,6 +545,8 @@ _TENSOR_SOURCES = ("inflx_tensor_kernels.hip", "inflx_tensor.h", "inflx_tensor_a
 _DELTAN_SOURCES = ("inflx_deltan_kernels.hip", "inflx_deltan.h", "inflx_deltan_abi.h", "inflx_background.h", "inflx_background_abi.h")
 _EVOLUTION_SOURCES = ("inflx_evolution_kernels.hip", "inflx_evolution.h", "inflx_evolution_abi.h", "inflx_modes.h", "inflx_modes_abi.h", "inflx_background.h",
                       "inflx_background_abi.h")  # fmt: skip
+_STOCHASTIC_SOURCES = ("inflx_stochastic_kernels.hip", "inflx_stochastic.h", "inflx_stochastic_abi.h", "inflx_philox.h", "inflx_background.h",
+                       "inflx_background_abi.h")  # fmt: skip
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 

@@ -50,6 +50,7 @@
 #include "inflx_tensor_abi.h"
 #include "inflx_deltan_abi.h"
 #include "inflx_evolution_abi.h"
+#include "inflx_stochastic_abi.h"
 
 namespace {
 
@@ -370,7 +371,7 @@ struct TableRing {
 
 // The code objects beside the core object that the background solver's families live in (kCompanions describes them), and what a
 // handle holds of one: its module and its kernels, in the order of the description's names.
-enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kCompanionCount };
+enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kObjStochastic, kCompanionCount };
 constexpr int kCompanionKernels = 10;  // the most kernels of one object (background)
 struct CompanionSlot {
   hipModule_t module = nullptr;
@@ -2892,7 +2893,7 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* mm, int op, const double* p, siz
 }  // extern "C"
 
 // ---- the background solver: what its families share ---------------------------------------------------------------------------
-// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution -- has its kernels in
+// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution, stochastic e-folds -- has its kernels in
 // a code object of its own beside the core object, `<artefact>.<suffix>`, which CompilationArtifact.ensure_<suffix>() builds.
 // kCompanions has one constant description per object: the words of its messages, its layout word, its kernels.  need_companion
 // loads any of them into its slot of the handle on first use, and a call site names a kernel by its family's index below.  The
@@ -2910,6 +2911,7 @@ static_assert(kAbiMajor == INFLX_MD_DEFAULT_ABI_MAJOR, "a modes object reports t
 static_assert(kAbiMajor == INFLX_TN_DEFAULT_ABI_MAJOR, "a tensor object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_DN_DEFAULT_ABI_MAJOR, "a delta-N object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_EV_DEFAULT_ABI_MAJOR, "an evolution object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_ST_DEFAULT_ABI_MAJOR, "a stochastic object reports the core object's ABI major: change both together");
 
 struct CompanionDesc {
   const char* suffix;      // the file is `<artefact>.<suffix>` and CompilationArtifact.ensure_<suffix>() builds it
@@ -2925,6 +2927,7 @@ enum BgKernel { kBgInit, kBgRowsTranspose, kBgAdvance /* + 2 method + store rows
 enum StateKernel { kStates };                                // kinematics, masses
 enum LaneKernel { kLaneInit, kLaneAdvance /* + method */ };  // transfer, modes, tensor, evolution
 enum DnKernel { kDnInit, kDnReduce, kDnEnd /* + method: phase A */, kDnSurface = 4 /* + method: phase B */ };
+enum StKernel { kStInit, kStReduce, kStAdvance /* + method */ };
 const CompanionDesc kCompanions[kCompanionCount] = {
     {"background", "background kernels", "are", "inflatox_amd.background", "INFLX_BG_ABI", INFLX_BG_ABI_VERSION,
      {"inflx_bg_init", "inflx_bg_rows_transpose", "inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows", "inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows",
@@ -2941,6 +2944,8 @@ const CompanionDesc kCompanions[kCompanionCount] = {
      {"inflx_dn_init", "inflx_dn_reduce", "inflx_dn_end_rk4", "inflx_dn_end_rkf", "inflx_dn_surface_rk4", "inflx_dn_surface_rkf"}},
     {"evolution", "evolution kernels", "are", "inflatox_amd.background.spectra_evolution", "INFLX_EV_ABI", INFLX_EV_ABI_VERSION,
      {"inflx_ev_init", "inflx_ev_advance_rk4", "inflx_ev_advance_rkf"}},
+    {"stochastic", "stochastic kernels", "are", "inflatox_amd.background.stochastic_efolds", "INFLX_ST_ABI", INFLX_ST_ABI_VERSION,
+     {"inflx_st_init", "inflx_st_reduce", "inflx_st_advance_rk4", "inflx_st_advance_rkf"}},
 };
 
 // Load the companion object `which` beside the core object, unless the handle has it: it must carry the core object's VERSION and
@@ -3855,6 +3860,97 @@ int inflx_delta_n(inflx_model* m, const double* p, size_t P, size_t n_p, const d
       if (surface) {
         surface[c0 + l] = host_surface[l];
         surface[B + c0 + l] = h_end ? std::numeric_limits<double>::quiet_NaN() : host_surface[nb + l];
+      }
+    }
+  }
+  return sf_verdict(m);
+}
+
+}  // extern "C"
+
+// ---- stochastic e-folds: Langevin noise on every lane, moments of N over the realisations (inflx_stochastic_efolds) ----------------
+extern "C" {
+
+int inflx_stochastic_efolds(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t R, const uint32_t* streams, uint64_t seed,
+                            double noise_scale, double dN_max, double N_stop, size_t max_steps, int method, double max_err, double dt, double* moments,
+                            double* samples) {
+  INFLX_SERIALISE(m);
+  auto noise = [&]() -> int {
+    if (R < 1 || R > INFLX_ST_MAX_REALISATIONS) return fail(INFLX_ERR_ARG, "the number of realisations must be in [1, 2^20] (got %zu)", R);
+    if (!(noise_scale >= 0.0) || !std::isfinite(noise_scale)) return fail(INFLX_ERR_ARG, "noise_scale must be a finite number >= 0");
+    if (!(dN_max > 0.0)) return fail(INFLX_ERR_ARG, "dN_max must be positive (it may be infinite)");
+    if (!std::isnan(N_stop) && !(N_stop > 0.0)) return fail(INFLX_ERR_ARG, "N_stop must be positive, or NaN for none");
+    return INFLX_OK;
+  };
+  // (the call has no flags, and its results are the moments: there is no status array)
+  int rc = check_integrator_args(m, "the stochastic e-folds require", "point", p, P, n_p, B, method, 0, 0, noise, max_steps, max_err, dt, /*status=*/m);
+  if (rc) return rc;
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  if (!moments) return fail(INFLX_ERR_ARG, "moments array is NULL");
+  if ((uint64_t)B > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of points must be below 2^32 (got %zu)", B);
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_companion(m, kObjStochastic))) return rc;
+  const CompanionSlot& st = m->companion[kObjStochastic];
+  hipStream_t s = m->stream;
+  const int mi = method == INFLX_EOM_RKF ? 1 : 0;
+  // a pass holds whole points: as many as the lanes of a pass of the solver allow (R <= 2^20 = kBgMaxLanes: at least one)
+  const size_t lanes_max = inflx_bg_lanes_per_pass(B * R, INFLX_ST_CARRY_PLANES * sizeof(double), INFLX_ST_THREADS);
+  const size_t nb_max = std::min(B, std::max<size_t>(1, lanes_max / R));
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_init = nullptr, *d_carry = nullptr, *d_out = nullptr;
+  uint32_t *d_streams = nullptr, *d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nb_max * 4)) || (rc = dev.array(&d_streams, nb_max)) ||
+      (rc = dev.array(&d_carry, nb_max * R * INFLX_ST_CARRY_PLANES)) || (rc = dev.array(&d_out, nb_max * INFLX_ST_OUT_PLANES)) || (rc = dev.array(&d_running, 1)))
+    return rc;
+  auto grid_of = [](size_t lanes) { return (unsigned)((lanes + INFLX_ST_THREADS - 1) / INFLX_ST_THREADS); };
+  std::vector<uint32_t> host_streams(nb_max);
+  std::vector<double> host_carry(samples ? nb_max * R * INFLX_ST_CARRY_PLANES : 0);
+
+  for (size_t c0 = 0; c0 < B; c0 += nb_max) {
+    const size_t nb = std::min(nb_max, B - c0), lanes = nb * R;
+    for (size_t b = 0; b < nb; ++b) host_streams[b] = streams ? streams[c0 + b] : (uint32_t)(c0 + b);
+    InflxStArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = d_init;
+    a.streams = d_streams;
+    a.carry = d_carry;
+    a.running = d_running;
+    a.nb = nb;
+    a.seed = seed;
+    a.R = (uint32_t)R;
+    a.noise_scale = noise_scale;
+    a.dn_max = dN_max;
+    a.n_stop = N_stop;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    void* params[] = {&a};
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, nb * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_streams, host_streams.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipModuleLaunchKernel(st.fn[kStInit], grid_of(lanes), 1, 1, INFLX_ST_THREADS, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(st.fn[kStAdvance + mi], a, grid_of(lanes), INFLX_ST_THREADS, max_steps, s))) return rc;
+    InflxStReduceArgs r;
+    memset(&r, 0, sizeof r);
+    r.carry = d_carry;
+    r.out = d_out;
+    r.nb = nb;
+    r.R = (uint32_t)R;
+    void* rparams[] = {&r};
+    HIP_TRY(hipModuleLaunchKernel(st.fn[kStReduce], (unsigned)nb, 1, 1, INFLX_ST_THREADS, 1, 1, 0, s, rparams, nullptr));
+    // the planes as they are: a plane of this pass's points is nb doubles, B doubles apart in `moments`
+    HIP_TRY(hipMemcpy2DAsync(moments + c0, B * sizeof(double), d_out, nb * sizeof(double), nb * sizeof(double), INFLX_ST_OUT_PLANES, hipMemcpyDeviceToHost, s));
+    if (samples) HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry, lanes * INFLX_ST_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (samples) {
+      const double* hc = host_carry.data();
+      const size_t total = B * R, base = c0 * R;
+      for (size_t l = 0; l < lanes; ++l) {
+        const double status = hc[(size_t)INFLX_ST_CARRY_STATUS * lanes + l];
+        samples[base + l] = (int)status == INFLX_EOM_ENDED ? hc[(size_t)INFLX_ST_CARRY_RESULT * lanes + l] : hc[(size_t)(INFLX_ST_CARRY_Y + 5) * lanes + l];
+        for (int c = 0; c < 5; ++c) samples[(size_t)(1 + c) * total + base + l] = hc[(size_t)(INFLX_ST_CARRY_Y + c) * lanes + l];
+        samples[(size_t)6 * total + base + l] = status;
       }
     }
   }

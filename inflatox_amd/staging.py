@@ -1219,3 +1219,77 @@ def emit_masses_header(model, param_slots: dict, cse=None, cse_vector=None) -> s
         + "\n".join(lines)
         + "\n}\n"
     )
+
+
+def emit_noise_header(model, param_slots: dict, cse=None, cse_vector=None) -> str:
+    """The geometry of a stochastic kick at one point, for the Langevin steps of the stochastic e-folds (csrc/inflx_stochastic.h):
+    ``inflx_noise_point(x0, x1, args, o)`` writes ``o[0..2]`` = e_00, e_10, e_11, the lower-triangular factor of the inverse metric,
+    e e^T = G^-1 (e_00 = sqrt(g11 / det), e_10 = -g01 / (det e_00), e_11 = 1 / sqrt(g11)), and ``o[3..4]`` = Gamma^a = G^bc Gamma^a_bc,
+    the contracted connection of the Ito term.
+
+    Gamma^a is derived here from ``model.metric`` and the adjugate adj of the 2 x 2 metric, like ``emit_masses_header``'s connection,
+    but in the contracted form Gamma^a = -(1 / sqrt(det)) d_b (adj^ab / sqrt(det)) = -sum_b d_b q^ab / (2 adj^ab) with q^ab = (adj^ab)^2 /
+    det, each ratio and each quotient reduced by ``sympy.cancel`` before anything is printed.  The sum over first-kind symbols, adj^bc
+    adj^as [bc, s] / det^2, is the same function, but where the components of the metric share a factor (the D5 model: both carry one
+    square root) the derivatives of that factor cancel between its terms only in exact arithmetic, and binary64 keeps 1e-7 to 1e-10
+    of the result; in q^ab the factor is gone before the derivative is taken, and the reduced quotient has no pole where an
+    off-diagonal component vanishes.
+
+    A header of its own, read only by the stochastic code object (``CompilationArtifact.ensure_stochastic``).  Written like
+    ``emit_masses_header``: staged with every stage inline in one function, the model's ``cse`` setting (Gamma^a, and the metric,
+    each through ``cse_vector``); metric components that print as zero are skipped."""
+    if model.dim != 2:
+        raise ValueError("the stochastic kick needs a two-field model")
+    x = list(model.coordinates)
+    x0, x1 = x
+    g = [[sympy.sympify(model.metric[i][j]) for j in range(2)] for i in range(2)]
+    metric = [g[i][j] for i in range(2) for j in range(2)]
+    det = g[0][0] * g[1][1] - g[0][1] * g[1][0]
+    adj = [[g[1][1], -g[0][1]], [-g[1][0], g[0][0]]]
+
+    contracted = []
+    for a in range(2):
+        total = sympy.Integer(0)
+        for b in range(2):
+            if adj[a][b] != 0:
+                total -= sympy.cancel(sympy.diff(sympy.cancel(adj[a][b] ** 2 / det), x[b]) / (2 * adj[a][b]))
+        contracted.append(total)
+    plain = C99CodePrinter()._print_Symbol
+    names = {x0: "x0", x1: "x1"}
+    for sym in set().union(*[sympy.sympify(e).free_symbols for e in contracted + metric]) - set(names):
+        names[sym] = param_slots[plain(sym)]
+    functions = [cse_vector(contracted) if cse_vector is not None else ([], contracted), cse_vector(metric) if cse_vector is not None else ([], metric)]
+    st = Stager(functions, x0, x1, names, staged=True)
+    lines = [ln for m in (U, R, C, P) for ln in st.lines[m]]
+    texts = list(st.outputs)
+    lines += [f"  const double gam0 = {texts[0]};", f"  const double gam1 = {texts[1]};"]
+    have = set()
+    for i in range(2):
+        for j in range(2):
+            t = texts[2 + 2 * i + j]
+            if t in ("0", "0.0"):
+                continue
+            have.add((i, j))
+            lines.append(f"  const double g{i}{j} = {t};")
+    off_diagonal = {(0, 1), (1, 0)} <= have
+    det_text = ("g00 * g11" if {(0, 0), (1, 1)} <= have else "0.0") + (" - g01 * g10" if off_diagonal else "")
+    g11 = "g11" if (1, 1) in have else "0.0"
+    lines += [
+        "  const double det = " + det_text + ";",
+        f"  const double e00 = sqrt({g11} / det);",
+        "  o[0] = e00;",
+        "  o[1] = " + ("-g01 / (det * e00)" if off_diagonal else "0.0") + ";",
+        f"  o[2] = 1.0 / sqrt({g11});",
+        "  o[3] = gam0;",
+        "  o[4] = gam1;",
+    ]
+    return (
+        "// Generated by inflatox_amd.Compiler -- do not edit.\n"
+        f"// factor of the inverse metric and contracted connection of model {model.model_name} (csrc/inflx_stochastic.h); needs the model's core header first\n"
+        "#pragma once\n"
+        "// o[0..2]: e_00, e_10, e_11 with e e^T = G^-1, e lower triangular;  o[3..4]: Gamma^a = G^bc Gamma^a_bc\n"
+        "INFLX_FN void inflx_noise_point([[maybe_unused]] const double x0, [[maybe_unused]] const double x1, [[maybe_unused]] const double* __restrict__ args, "
+        "double* __restrict__ o) {\n"
+        + "\n".join(lines)
+        + "\n}\n"
+    )
