@@ -13,6 +13,10 @@ must mean the same thing here and there.
 
 The generator draws potentials and diagonal metrics from a small grammar of smooth, positive-where-needed building blocks, so that
 every model is well defined on its grid; with `cse=True` for every second model (the reference's per-function sympy.cse path).
+
+Both sides of these comparisons share this repository's symbolic stage (oracle.emit_c_source prints the expressions it derived), and
+every metric here is diagonal.  tests/test_sweep_truth.py checks the same 24 models, and models with G_01 != 0, against a 50-digit
+derivation that starts from (fields, metric, potential) alone (tests/sweep_truth.py); tests/test_sweep_truth_gpu.py does so on the GPU.
 """
 
 import functools
