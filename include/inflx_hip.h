@@ -676,5 +676,7 @@ int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p
 #include "inflx_hip_evolution.h"
 /* stochastic e-folds (Langevin noise on every trajectory, moments of N over the realisations): likewise */
 #include "inflx_hip_stochastic.h"
+/* first-passage histograms (the distribution of N over realisations on lanes that are used again): likewise */
+#include "inflx_hip_distribution.h"
 
 #endif /* INFLX_HIP_H */

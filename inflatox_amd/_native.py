@@ -157,6 +157,17 @@ STOCHASTIC_SIGNATURES = {
          _DP, _DP],
     ),
 }
+# ... and for include/inflx_hip_distribution.h
+DISTRIBUTION_SIGNATURES = {
+    "inflx_stochastic_distribution": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint64, _SIZE, C.c_double, C.c_double, _SIZE, C.c_int, C.c_double,
+         C.c_double, _SIZE, _DP, _SIZE, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    ),
+}
+PD_MAX_REALISATIONS = (1 << 32) - 1
+PD_MAX_BINS = 1 << 20
+PD_MAX_LANES_PER_POINT = 1 << 20
 ST_OUT_PLANES = 12  # mean, m2, m3, m4, min, max, lanes per status 0..5
 ST_SAMPLE_PLANES = 7  # N, phi^0, phi^1, chi^0, chi^1, H, status
 ST_MAX_REALISATIONS = 1 << 20
@@ -177,7 +188,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h"), os.path.join(_PKG, "csrc", "inflx_stochastic_abi.h"), os.path.join(_REPO, "include", "inflx_hip_stochastic.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h"), os.path.join(_PKG, "csrc", "inflx_stochastic_abi.h"), os.path.join(_REPO, "include", "inflx_hip_stochastic.h"), os.path.join(_PKG, "csrc", "inflx_distribution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_distribution.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -233,7 +244,8 @@ def load_library():
             )
         _preload_hip_runtime()
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items(), *EVOLUTION_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items(), *EVOLUTION_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items(),
+                                  *DISTRIBUTION_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -783,6 +795,39 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return moments, samples
+
+    # ---- first-passage histograms (include/inflx_hip_distribution.h: inflx_stochastic_distribution) --------------
+    def stochastic_distribution(self, p, init, R: int, streams, seed: int, first: int, lanes_per_point: int, noise_scale: float, dn_max: float, max_steps: int,
+                                method: int, max_err: float, dt: float, bins: int, ranges):
+        """B points from ``init`` (B,4), the realisations ``first`` .. ``first + R - 1`` of the Langevin equation each on
+        ``lanes_per_point`` lanes that are used again (0: the library's choice); ``streams`` (B,) uint32 or None (the point's index);
+        ``ranges`` (1, 2) or (B, 2): lo and hi of the ``bins`` bins.  Returns (hist (B, bins + 2) uint32: below, the bins, above over the
+        realisations that ended inflation; counts (B, 6) uint32: the realisations per status 0..5).  The distribution object must be
+        in place (``CompilationArtifact.ensure_distribution``)."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        ranges = _f64(ranges, "ranges")
+        B = init.shape[0]
+        if ranges.ndim != 2 or ranges.shape[1] != 2 or ranges.shape[0] not in (1, B):
+            raise InflatoxShapeError(f"ranges must have shape (1, 2) or ({B}, 2) (got {ranges.shape})")
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint32)
+            if streams.shape != (B,):
+                raise InflatoxShapeError(f"streams must have shape ({B},) (got {streams.shape})")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        # (a number of bins the library refuses is refused before it writes: the rows need not hold that many)
+        hist = np.zeros((B, min(max(int(bins), 0), PD_MAX_BINS) + 2), dtype=np.uint32)
+        counts = np.zeros((B, 6), dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        _check(
+            self._lib.inflx_stochastic_distribution(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(R), None if streams is None else streams.ctypes.data_as(u32), int(seed), int(first),
+                int(lanes_per_point), float(noise_scale), float(dn_max), int(max_steps), int(method), float(max_err), float(dt), int(bins), _ptr(ranges),
+                ranges.shape[0], hist.ctypes.data_as(u32), counts.ctypes.data_as(u32),
+            )
+        )  # fmt: skip
+        return hist, counts
 
     # ---- generalised sweeps -------------------------------------------------------------------
     def sweep_host(self, op, p, start_stop, N0, N1, row_begin=0, row_count=None, layout=LAYOUT_AOS) -> np.ndarray:

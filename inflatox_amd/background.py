@@ -30,7 +30,11 @@ along its evolution, from one integration of every lane; ``evolution_map`` is ``
 ``transfer_from_spectra`` reads the transfer functions T_RS and T_SS off such samples: the measured counterpart of ``transfer_functions``.
 ``stochastic_efolds`` adds the Langevin noise of the separate-universe picture to every trajectory -- a field kick of variance (H / 2 pi)^2
 per e-fold, right on a curved field space -- and returns the moments of the e-fold count over many realisations of every point, the
-input of the stochastic delta-N formalism; ``stochastic_map`` places the points on a sweep grid.
+input of the stochastic delta-N formalism; ``stochastic_map`` places the points on a sweep grid.  ``stochastic_distribution`` returns the
+distribution P(N) itself, a histogram per point over up to 2^32 - 1 realisations run on GPU lanes that are used again as realisations
+finish, and ``stochastic_distribution_map`` places the points on a sweep grid; ``distribution_pdf``, ``distribution_survival``,
+``distribution_mean`` and ``distribution_tail_rate`` read a density, the survival function, the mean and the rate of an exponential
+tail off such a histogram on the host.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -58,7 +62,8 @@ __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map
            "SampledSolution", "STATUS", "kinematics", "turn_rate_map", "Kinematics", "masses", "mass_map", "Masses", "transfer_functions", "transfer_map",
            "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra", "tensor_spectra", "TensorSpectra", "observables", "Observables", "observables_map",
            "delta_N", "DeltaN", "fnl_map", "delta_N_status", "spectra_evolution", "SpectraEvolution", "evolution_map", "transfer_from_spectra",
-           "stochastic_efolds", "stochastic_map", "StochasticEfolds"]  # fmt: skip
+           "stochastic_efolds", "stochastic_map", "StochasticEfolds", "stochastic_distribution", "stochastic_distribution_map", "StochasticDistribution",
+           "distribution_pdf", "distribution_survival", "distribution_mean", "distribution_tail_rate"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -1557,3 +1562,253 @@ def stochastic_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1:
     R, seed, noise_scale, dN_max, N_stop, max_steps, max_err, dt = options
     flat = _stochastic_run(artifact, p, init, R, None, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt, False)
     return StochasticEfolds(*(a.reshape(N0, N1, *a.shape[1:]) for a in flat[:9]))
+
+
+class StochasticDistribution(NamedTuple):
+    """What :func:`stochastic_distribution` returns (``stochastic_distribution_map``: (N0, N1) in place of (B,)).  ``hist`` (B, bins)
+    int64: the realisations that ENDED inflation per bin of the e-fold count N_end; ``below`` and ``above`` (B,): those outside the
+    range.  The bin of N is k = floor((N - lo) * (bins / (hi - lo))) in binary64 -- N < lo is below, k >= bins is above, so N = hi is
+    above --: that rule is the definition, and ``edges`` (B, bins + 1), lo + k (hi - lo) / bins, are nominal.  ``counts`` (B, 6): the
+    realisations per ``STATUS`` code 0..5 and ``n_ended`` = counts[:, ENDED] = below + hist.sum(-1) + above.  ``N_classical``: the
+    e-fold count of the trajectory without noise (NaN where it did not end); with ``centre="classical"`` such a point is not run: its
+    counts are zero and its edges NaN.  ``realisations``, ``first_realisation`` and ``seed`` are the call's: the realisations are
+    first_realisation .. first_realisation + realisations - 1.  Two results of the same edges and seed whose ranges of realisations
+    adjoin add up with ``+`` to the result of the call over both ranges, exactly."""
+
+    hist: np.ndarray
+    below: np.ndarray
+    above: np.ndarray
+    edges: np.ndarray
+    counts: np.ndarray
+    n_ended: np.ndarray
+    N_classical: np.ndarray
+    realisations: int
+    first_realisation: int
+    seed: int = 0
+
+    def __add__(self, other):
+        if not isinstance(other, StochasticDistribution):
+            return NotImplemented
+        a, b = (self, other) if self.first_realisation <= other.first_realisation else (other, self)
+        if a.seed != b.seed:
+            raise ValueError(f"the two distributions have different seeds ({a.seed} and {b.seed})")
+        if np.shape(a.edges) != np.shape(b.edges) or not np.array_equal(a.edges, b.edges, equal_nan=True):
+            raise ValueError("the two distributions have different edges")
+        if a.first_realisation + a.realisations != b.first_realisation:
+            raise ValueError(f"the realisations do not adjoin: [{a.first_realisation}, {a.first_realisation + a.realisations}) and "
+                             f"[{b.first_realisation}, {b.first_realisation + b.realisations})")  # fmt: skip
+        return StochasticDistribution(a.hist + b.hist, a.below + b.below, a.above + b.above, a.edges, a.counts + b.counts, a.n_ended + b.n_ended, a.N_classical,
+                                      a.realisations + b.realisations, a.first_realisation, a.seed)  # fmt: skip
+
+
+def _check_distribution_options(artifact, realisations, bins, centre, seed, first_realisation, lanes_per_point, noise_scale, dN_max, max_steps, max_err, solver, dt):
+    """The checks ``stochastic_distribution`` and ``stochastic_distribution_map`` share: (R, bins, seed, first, L (0: the library's
+    choice), noise_scale, dN_max, max_steps, max_err, dt)."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    try:
+        R, bins, seed, first = operator.index(realisations), operator.index(bins), operator.index(seed), operator.index(first_realisation)
+        L = 0 if lanes_per_point is None else operator.index(lanes_per_point)
+    except TypeError:
+        raise ValueError("realisations, bins, seed, first_realisation and lanes_per_point must be integers") from None
+    if R < 1 or R > _native.PD_MAX_REALISATIONS:
+        raise ValueError(f"realisations must be in [1, 2^32 - 1] (got {R})")
+    if bins < 1 or bins > _native.PD_MAX_BINS:
+        raise ValueError(f"bins must be in [1, 2^20] (got {bins})")
+    if seed < 0 or seed >= 2**64:
+        raise ValueError(f"seed must be in [0, 2^64) (got {seed})")
+    if first < 0 or first + R > 2**32:
+        raise ValueError(f"first_realisation must be >= 0 and first_realisation + realisations at most 2^32 (got {first} + {R})")
+    if lanes_per_point is not None and (L < 64 or L % 64 or L > _native.PD_MAX_LANES_PER_POINT):
+        raise ValueError(f"lanes_per_point must be None or a multiple of 64 in [64, 2^20] (got {L})")
+    if centre not in (None, "classical"):
+        raise ValueError(f'centre must be None or "classical" (got {centre!r})')
+    try:
+        noise_scale, dN_max = float(noise_scale), float(dN_max)
+    except (TypeError, ValueError):
+        raise ValueError("noise_scale and dN_max must be numbers") from None
+    if not (math.isfinite(noise_scale) and noise_scale >= 0.0):
+        raise ValueError(f"noise_scale must be finite and >= 0 (got {noise_scale})")
+    if not dN_max > 0.0:
+        raise ValueError(f"dN_max must be positive (got {dN_max})")
+    return R, bins, seed, first, L, noise_scale, dN_max, max_steps, max_err, dt
+
+
+def _check_n_range(N_range, B):
+    """``N_range`` as (1, 2) or (B, 2): finite, hi above lo"""
+    try:
+        r = np.array(N_range, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("N_range must be numbers") from None
+    if r.shape == (2,):
+        r = r.reshape(1, 2)
+    if r.ndim != 2 or r.shape[1] != 2 or r.shape[0] not in (1, B):
+        raise InflatoxShapeError(f"N_range must be (lo, hi) or have shape ({B}, 2) (got {r.shape})")
+    with np.errstate(over="ignore", invalid="ignore"):
+        finite = np.all(np.isfinite(r)) and np.all(np.isfinite(r[:, 1] - r[:, 0]))
+    if not finite:
+        raise ValueError("N_range must be finite (and so its width)")
+    if not np.all(r[:, 1] > r[:, 0]):
+        raise ValueError("N_range is empty: hi must be above lo")
+    return r
+
+
+def _distribution_run(artifact, p, init, ranges, ids, centre, options, solver) -> StochasticDistribution:
+    R, bins, seed, first, L, noise_scale, dN_max, max_steps, max_err, dt = options
+    artifact.ensure_stochastic()
+    artifact.ensure_distribution()
+    lib = _dylib(artifact, background=False)
+    method, B = _METHODS[solver], init.shape[0]
+    ids = np.arange(B, dtype=np.uint32) if ids is None else ids
+    # the classical trajectory as _stochastic_run finds it: one realisation and no noise (moments: its N_end is the mean)
+    classical, _ = lib.stochastic_efolds(p, init, 1, ids, seed, 0.0, dN_max, math.nan, max_steps, method, max_err, dt or 0.0)
+    n_classical = np.where(classical[6 + ENDED] == 1.0, classical[0], np.nan)
+    ranges = np.broadcast_to(ranges, (B, 2)).copy()
+    run = np.ones(B, dtype=bool)
+    if centre == "classical":
+        run = np.isfinite(n_classical)
+        ranges = ranges + np.where(run, n_classical, np.nan)[:, None]
+        if not np.all(ranges[run, 1] > ranges[run, 0]):
+            raise ValueError("N_range is empty beside the classical e-fold count: hi must be above lo")
+    hist = np.zeros((B, bins + 2), dtype=np.int64)
+    counts = np.zeros((B, 6), dtype=np.int64)
+    if run.any():
+        rows = p if p.ndim == 1 else np.ascontiguousarray(p[run])
+        h, c = lib.stochastic_distribution(rows, np.ascontiguousarray(init[run]), R, np.ascontiguousarray(ids[run]), seed, first, L, noise_scale, dN_max, max_steps,
+                                           method, max_err, dt or 0.0, bins, np.ascontiguousarray(ranges[run]))  # fmt: skip
+        hist[run], counts[run] = h, c
+    edges = ranges[:, :1] + np.arange(bins + 1, dtype=np.float64) * ((ranges[:, 1:] - ranges[:, :1]) / bins)
+    return StochasticDistribution(hist[:, 1:-1], hist[:, 0], hist[:, -1], edges, counts, counts[:, ENDED], n_classical, R, first, seed)
+
+
+def stochastic_distribution(artifact: CompilationArtifact, pars, fields_init, derivatives_init, realisations: int, bins: int, N_range, *, centre: str | None = None,
+                            seed: int = 0, streams=None, first_realisation: int = 0, lanes_per_point: int | None = None, noise_scale: float = 1.0,
+                            dN_max: float = 1.0 / 32.0, max_steps: int = 1_000_000, max_err: float = 1e-8, solver: str = "rkf",
+                            dt: float | None = None) -> StochasticDistribution:  # fmt: skip
+    """The distribution P(N) of the e-fold count to the end of inflation, as a histogram per point: ``realisations`` (R, up to
+    2^32 - 1 -- no chunking is needed) solutions of ``stochastic_efolds``' Langevin equation from each of the B states ``fields_init``,
+    ``derivatives_init`` (both (B, 2)), binned on the GPU the moment they end.  The tail of P(N), which four moments do not show, sets
+    the abundance of primordial black holes in stochastic delta-N.
+
+    Every point has ``lanes_per_point`` GPU lanes (a multiple of 64; None: the smallest multiple of 64 that is >= R, but no more than
+    an equal share, floor(2^20 / B), of the 2^20 lanes of one pass, and no less than 64: few points get many lanes each).  A lane runs
+    a realisation to its stop, counts it, draws the point's next ticket and starts that realisation afresh from the point's initial
+    state; no lane idles while its point has tickets, and memory is O(lanes + bins), not O(R).  Realisation r is the one
+    ``stochastic_efolds`` runs for the same ``seed``, stream and r -- its random numbers are keyed by (seed; its own accepted-step
+    index, r, stream) -- and counts are integers, so the result does not depend on ``lanes_per_point`` or on scheduling, bit for
+    bit; it is the binning of ``stochastic_efolds(..., return_samples=True).N`` where that call is possible.
+
+    ``N_range`` is (lo, hi) for all points or (B, 2); with ``centre="classical"`` it holds offsets from every point's classical
+    e-fold count (one run without noise, ``N_classical``), and a point whose classical run does not end is not run: zero counts, NaN
+    edges.  ``bins`` in [1, 2^20]; the bin rule is :class:`StochasticDistribution`'s.  The realisations are ``first_realisation`` ..
+    ``first_realisation + R - 1`` (at most 2^32 in all), so that calls over adjoining ranges add up (``+``) to the call over their
+    union.  ``streams``, ``noise_scale``, ``dN_max``, ``max_steps``, ``max_err``, ``solver`` and ``dt`` are ``stochastic_efolds``';
+    there is no ``N_stop`` (every N would be the same).  Only realisations that ENDED inflation are binned: ``counts`` says what became
+    of all R, and a realisation that ran out of ``max_steps`` counts as ``COMPLETE`` -- where ``n_ended < R`` the histogram misses the
+    long realisations, which are the tail.  The kernels are csrc/inflx_distribution_kernels.hip, built into
+    ``<artefact>.distribution`` on first use (``CompilationArtifact.ensure_distribution``).  Bad arguments raise before anything
+    runs on the device."""
+    options = _check_distribution_options(artifact, realisations, bins, centre, seed, first_realisation, lanes_per_point, noise_scale, dN_max, max_steps, max_err,
+                                          solver, dt)  # fmt: skip
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    B = x.shape[0]
+    ids = _check_streams(streams, B)
+    p = _pars(artifact, pars, B)
+    ranges = _check_n_range(N_range, B)
+    return _distribution_run(artifact, p, np.concatenate([x, v], axis=1), ranges, ids, centre, options, solver)
+
+
+def stochastic_distribution_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, realisations: int, bins: int, N_range, *,
+                                centre: str | None = "classical", derivatives_init=(0.0, 0.0), seed: int = 0, first_realisation: int = 0,
+                                lanes_per_point: int | None = None, noise_scale: float = 1.0, dN_max: float = 1.0 / 32.0, max_steps: int = 1_000_000,
+                                max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None) -> StochasticDistribution:  # fmt: skip
+    """``stochastic_distribution`` from every point of an (N0, N1) grid over ``start_stop`` (the sweeps' layout and coordinate rule,
+    ``grid_points``), all trajectories starting with the velocities ``derivatives_init``: the same result as (N0, N1, ...) maps
+    (``hist`` (N0, N1, bins), ``edges`` (N0, N1, bins + 1), ``counts`` (N0, N1, 6)), the stream of a point its index in the flattened
+    grid.  ``N_range`` is (lo, hi) or (N0 * N1, 2) and by default holds offsets from every point's classical e-fold count
+    (``centre="classical"``): one range then serves a grid whose points are at very different distances from the end of inflation.
+    A grid point whose classical run does not end has zero counts and NaN edges."""
+    options = _check_distribution_options(artifact, realisations, bins, centre, seed, first_realisation, lanes_per_point, noise_scale, dN_max, max_steps, max_err,
+                                          solver, dt)  # fmt: skip
+    ss = np.asarray(start_stop, dtype=np.float64)
+    if ss.size != 4:
+        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
+    N0, N1 = operator.index(N0), operator.index(N1)
+    if N0 < 1 or N1 < 1:
+        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
+    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
+    if d.size != 2:
+        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
+    p = _pars(artifact, pars, 1)
+    if p.ndim != 1:
+        raise InflatoxShapeError("stochastic_distribution_map takes one parameter row")
+    ranges = _check_n_range(N_range, N0 * N1)
+    x0, x1 = grid_points(ss, N0, N1)
+    init = np.empty((N0 * N1, 4))
+    init[:, 0] = np.repeat(x0, N1)
+    init[:, 1] = np.tile(x1, N0)
+    init[:, 2:] = d
+    flat = _distribution_run(artifact, p, init, ranges, None, centre, options, solver)
+    return StochasticDistribution(*(a.reshape(N0, N1, *a.shape[1:]) for a in flat[:7]), *flat[7:])
+
+
+def _distribution_width(d: StochasticDistribution):
+    bins = d.hist.shape[-1]
+    return (d.edges[..., -1] - d.edges[..., 0]) / bins
+
+
+def distribution_pdf(d: StochasticDistribution) -> np.ndarray:
+    """The density of N_end over the realisations that ended inflation, hist / (n_ended width), same shape as ``hist``: it integrates
+    over the range to the share of them that fell inside it.  NaN where none ended."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return d.hist / (np.asarray(d.n_ended, dtype=np.float64) * _distribution_width(d))[..., None]
+
+
+def distribution_survival(d: StochasticDistribution) -> np.ndarray:
+    """P(N_end >= edge) at every edge, (sum of hist from that bin on + above) / n_ended, shape of ``edges``: ratios of exact integers,
+    one rounding each.  NaN where none ended."""
+    tail = np.concatenate([np.cumsum(d.hist[..., ::-1], axis=-1)[..., ::-1], np.zeros_like(d.hist[..., :1])], axis=-1) + np.asarray(d.above)[..., None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return tail / np.asarray(d.n_ended, dtype=np.float64)[..., None]
+
+
+def distribution_mean(d: StochasticDistribution) -> np.ndarray:
+    """The mean of N_end FROM THE BINS: every count inside the range at the midpoint of its bin, ``below`` and ``above`` left out.  It is
+    within half a bin width of the mean of the realisations inside the range, not the mean of all of them (``stochastic_efolds`` has
+    that, for R <= 2^20).  NaN where no realisation fell inside."""
+    mid = 0.5 * (d.edges[..., :-1] + d.edges[..., 1:])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (d.hist * mid).sum(axis=-1) / d.hist.sum(axis=-1)
+
+
+def distribution_tail_rate(d: StochasticDistribution, N_from):
+    """The rate Lambda of an exponential tail P(N) ~ exp(-Lambda N) above ``N_from``, and its standard error: (rate, stderr), shaped
+    like ``n_ended``.  The tail starts at the first edge e at or after ``N_from`` (a number, or one per point); with the counts above
+    it at the midpoints of their bins and the ``above`` realisations censored at hi, the maximum-likelihood rate is
+
+        Lambda = n_in / (sum_k hist_k (mid_k - e) + above (hi - e)),        n_in = sum_k hist_k over the bins from e on,
+
+    and its standard error Lambda / sqrt(n_in).  The midpoints bias it by (Lambda width)^2 / 12, relative.  NaN where no count lies
+    above e inside the range, or ``N_from`` is above the range."""
+    bins = d.hist.shape[-1]
+    hist = d.hist.reshape(-1, bins)
+    edges = d.edges.reshape(-1, bins + 1)
+    above = np.asarray(d.above).reshape(-1)
+    start = np.broadcast_to(np.asarray(N_from, dtype=np.float64), np.shape(d.n_ended)).reshape(-1)
+    rate = np.full(hist.shape[0], np.nan)
+    err = np.full(hist.shape[0], np.nan)
+    for b in range(hist.shape[0]):
+        if not (np.isfinite(edges[b, 0]) and start[b] <= edges[b, -1]):
+            continue
+        k = int(np.searchsorted(edges[b], start[b], side="left"))
+        e = edges[b, k]
+        mid = 0.5 * (edges[b, k:-1] + edges[b, k + 1 :])
+        n_in = int(hist[b, k:].sum())
+        exposure = float((hist[b, k:] * (mid - e)).sum() + above[b] * (edges[b, -1] - e))
+        if n_in > 0 and exposure > 0.0:
+            rate[b] = n_in / exposure
+            err[b] = rate[b] / math.sqrt(n_in)
+    shape = np.shape(d.n_ended)
+    return rate.reshape(shape), err.reshape(shape)

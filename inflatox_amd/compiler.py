@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" / "stochastic" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" / "stochastic" / "distribution" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -416,6 +416,20 @@ class CompilationArtifact:
             lambda: [("INFLX_EOM_HEADER", "st{key}.eom.h", self.eom_header_text()), ("INFLX_NOISE_HEADER", "st{key}.noise.h", self.noise_header_text())],
         )  # fmt: skip
 
+    def ensure_distribution(self) -> str:
+        """Extension: build the distribution code object of this model -- the kernels of
+        ``inflatox_amd.background.stochastic_distribution`` (csrc/inflx_distribution_kernels.hip) -- and return its path,
+        ``shared_object_path + ".distribution"``, where ``libinflx_hip.so`` looks for it.  One hipcc step on first use from the core
+        object's header and options, the header of the equations of motion and the noise header, cached as ``<tag>.pd<hash>.hsaco``
+        (the hash covers the two generated headers and ``_DISTRIBUTION_SOURCES``, code only -- csrc/inflx_stochastic.h and
+        csrc/inflx_background.h among them, whose step and kick the kernels run); the object carries the core object's ``MODEL_TAG``
+        and a layout word of its own (``INFLX_PD_ABI``).  Like the other nine companion objects it lies outside the kernel groups, and
+        none of them is involved: not the stochastic object either."""
+        return self._ensure_companion(
+            "distribution", _DISTRIBUTION_SOURCES, "pd{key}.hsaco",
+            lambda: [("INFLX_EOM_HEADER", "pd{key}.eom.h", self.eom_header_text()), ("INFLX_NOISE_HEADER", "pd{key}.noise.h", self.noise_header_text())],
+        )  # fmt: skip
+
     def ensure_rowpass(self) -> str | None:
         """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
         evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
@@ -547,6 +561,8 @@ _EVOLUTION_SOURCES = ("inflx_evolution_kernels.hip", "inflx_evolution.h", "inflx
                       "inflx_background_abi.h")  # fmt: skip
 _STOCHASTIC_SOURCES = ("inflx_stochastic_kernels.hip", "inflx_stochastic.h", "inflx_stochastic_abi.h", "inflx_philox.h", "inflx_background.h",
                        "inflx_background_abi.h")  # fmt: skip
+_DISTRIBUTION_SOURCES = ("inflx_distribution_kernels.hip", "inflx_distribution.h", "inflx_distribution_abi.h", "inflx_stochastic.h", "inflx_philox.h",
+                         "inflx_background.h", "inflx_background_abi.h")  # fmt: skip
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 

@@ -51,6 +51,7 @@
 #include "inflx_deltan_abi.h"
 #include "inflx_evolution_abi.h"
 #include "inflx_stochastic_abi.h"
+#include "inflx_distribution_abi.h"
 
 namespace {
 
@@ -371,7 +372,7 @@ struct TableRing {
 
 // The code objects beside the core object that the background solver's families live in (kCompanions describes them), and what a
 // handle holds of one: its module and its kernels, in the order of the description's names.
-enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kObjStochastic, kCompanionCount };
+enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kObjStochastic, kObjDistribution, kCompanionCount };
 constexpr int kCompanionKernels = 10;  // the most kernels of one object (background)
 struct CompanionSlot {
   hipModule_t module = nullptr;
@@ -2893,7 +2894,7 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* mm, int op, const double* p, siz
 }  // extern "C"
 
 // ---- the background solver: what its families share ---------------------------------------------------------------------------
-// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution, stochastic e-folds -- has its kernels in
+// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution, stochastic e-folds, first-passage histograms -- has its kernels in
 // a code object of its own beside the core object, `<artefact>.<suffix>`, which CompilationArtifact.ensure_<suffix>() builds.
 // kCompanions has one constant description per object: the words of its messages, its layout word, its kernels.  need_companion
 // loads any of them into its slot of the handle on first use, and a call site names a kernel by its family's index below.  The
@@ -2912,6 +2913,7 @@ static_assert(kAbiMajor == INFLX_TN_DEFAULT_ABI_MAJOR, "a tensor object reports 
 static_assert(kAbiMajor == INFLX_DN_DEFAULT_ABI_MAJOR, "a delta-N object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_EV_DEFAULT_ABI_MAJOR, "an evolution object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_ST_DEFAULT_ABI_MAJOR, "a stochastic object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_PD_DEFAULT_ABI_MAJOR, "a distribution object reports the core object's ABI major: change both together");
 
 struct CompanionDesc {
   const char* suffix;      // the file is `<artefact>.<suffix>` and CompilationArtifact.ensure_<suffix>() builds it
@@ -2928,6 +2930,7 @@ enum StateKernel { kStates };                                // kinematics, mass
 enum LaneKernel { kLaneInit, kLaneAdvance /* + method */ };  // transfer, modes, tensor, evolution
 enum DnKernel { kDnInit, kDnReduce, kDnEnd /* + method: phase A */, kDnSurface = 4 /* + method: phase B */ };
 enum StKernel { kStInit, kStReduce, kStAdvance /* + method */ };
+enum PdKernel { kPdInit, kPdAdvance /* + method */ };
 const CompanionDesc kCompanions[kCompanionCount] = {
     {"background", "background kernels", "are", "inflatox_amd.background", "INFLX_BG_ABI", INFLX_BG_ABI_VERSION,
      {"inflx_bg_init", "inflx_bg_rows_transpose", "inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows", "inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows",
@@ -2946,6 +2949,8 @@ const CompanionDesc kCompanions[kCompanionCount] = {
      {"inflx_ev_init", "inflx_ev_advance_rk4", "inflx_ev_advance_rkf"}},
     {"stochastic", "stochastic kernels", "are", "inflatox_amd.background.stochastic_efolds", "INFLX_ST_ABI", INFLX_ST_ABI_VERSION,
      {"inflx_st_init", "inflx_st_reduce", "inflx_st_advance_rk4", "inflx_st_advance_rkf"}},
+    {"distribution", "distribution kernels", "are", "inflatox_amd.background.stochastic_distribution", "INFLX_PD_ABI", INFLX_PD_ABI_VERSION,
+     {"inflx_pd_init", "inflx_pd_advance_rk4", "inflx_pd_advance_rkf"}},
 };
 
 // Load the companion object `which` beside the core object, unless the handle has it: it must carry the core object's VERSION and
@@ -3953,6 +3958,139 @@ int inflx_stochastic_efolds(inflx_model* m, const double* p, size_t P, size_t n_
         samples[(size_t)6 * total + base + l] = status;
       }
     }
+  }
+  return sf_verdict(m);
+}
+
+}  // extern "C"
+
+// ---- first-passage histograms: the distribution of N over realisations on lanes that are used again (inflx_stochastic_distribution) ----
+extern "C" {
+
+int inflx_stochastic_distribution(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t R, const uint32_t* streams, uint64_t seed,
+                                  uint64_t first_realisation, size_t lanes_per_point, double noise_scale, double dN_max, size_t max_steps, int method,
+                                  double max_err, double dt, size_t bins, const double* ranges, size_t n_ranges, uint32_t* hist, uint32_t* counts) {
+  INFLX_SERIALISE(m);
+  auto own = [&]() -> int {
+    if (R < 1 || (uint64_t)R > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of realisations must be in [1, 2^32 - 1] (got %zu)", R);
+    if (first_realisation > (UINT64_C(1) << 32) - (uint64_t)R)
+      return fail(INFLX_ERR_ARG, "first_realisation + realisations must not exceed 2^32 (got %llu + %zu)", (unsigned long long)first_realisation, R);
+    if (lanes_per_point % INFLX_PD_WAVE != 0 || lanes_per_point > INFLX_PD_MAX_LANES_PER_POINT)
+      return fail(INFLX_ERR_ARG, "lanes_per_point must be a multiple of 64 up to 2^20, or 0 for the library's choice (got %zu)", lanes_per_point);
+    if (bins < 1 || bins > INFLX_PD_MAX_BINS) return fail(INFLX_ERR_ARG, "bins must be in [1, 2^20] (got %zu)", bins);
+    if (n_ranges != 1 && n_ranges != B) return fail(INFLX_ERR_SHAPE, "range rows: %zu, expected 1 or one per point (%zu)", n_ranges, B);
+    if (!ranges) return fail(INFLX_ERR_ARG, "range array is NULL");
+    for (size_t k = 0; k < n_ranges; ++k) {
+      const double lo = ranges[2 * k], hi = ranges[2 * k + 1];
+      if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(hi - lo)) return fail(INFLX_ERR_ARG, "range %zu is not finite", k);
+      if (!(hi > lo)) return fail(INFLX_ERR_ARG, "range %zu is empty: hi must be above lo (got [%g, %g])", k, lo, hi);
+    }
+    if (!(noise_scale >= 0.0) || !std::isfinite(noise_scale)) return fail(INFLX_ERR_ARG, "noise_scale must be a finite number >= 0");
+    if (!(dN_max > 0.0)) return fail(INFLX_ERR_ARG, "dN_max must be positive (it may be infinite)");
+    return INFLX_OK;
+  };
+  // (the call has no flags, and its results are the counts: there is no status array)
+  int rc = check_integrator_args(m, "the first-passage histograms require", "point", p, P, n_p, B, method, 0, 0, own, max_steps, max_err, dt, /*status=*/m);
+  if (rc) return rc;
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  if (!hist || !counts) return fail(INFLX_ERR_ARG, "histogram or counts array is NULL");
+  if ((uint64_t)B > 0xffffffffu) return fail(INFLX_ERR_ARG, "the number of points must be below 2^32 (got %zu)", B);
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_companion(m, kObjDistribution))) return rc;
+  const CompanionSlot& pd = m->companion[kObjDistribution];
+  hipStream_t s = m->stream;
+  const int mi = method == INFLX_EOM_RKF ? 1 : 0;
+  // the lanes of a point.  The default: the smallest multiple of 64 that holds R -- a point with fewer realisations needs no more
+  // lanes --, but no more than an equal share of the 2^20 lanes of one pass, floor(2^20 / B) in whole wavefronts, and no less than 64:
+  // the B points fill one pass where R allows it and share one where B allows it.  (Few lanes per point leave the device idle
+  // where B is small: 3 points of 2^18 realisations took 0.30 s on 1024 lanes per point and 0.017 s on 2^18)  The result does not depend on it.
+  const size_t pass_lanes = inflx_bg_lanes_per_pass(kBgMaxLanes, INFLX_PD_CARRY_BYTES, INFLX_PD_THREADS);
+  size_t L = lanes_per_point;
+  if (L == 0) {
+    const size_t share = std::max<size_t>(INFLX_PD_WAVE, pass_lanes / B / INFLX_PD_WAVE * INFLX_PD_WAVE);
+    L = std::min<size_t>(((size_t)R + INFLX_PD_WAVE - 1) / INFLX_PD_WAVE * INFLX_PD_WAVE, share);
+  }
+  // a pass holds whole points: as many as the lanes of a pass allow (L <= 2^20 = kBgMaxLanes: at least one) and as the rows of counts
+  // fit the buffer of a pass's result
+  const size_t row = bins + 2;
+  const size_t nb_max = std::min({B, std::max<size_t>(1, pass_lanes / L), std::max<size_t>(1, kBgRowBytes / (row * sizeof(uint32_t)))});
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_init = nullptr, *d_bin = nullptr, *d_carry = nullptr;
+  uint64_t *d_words = nullptr, *d_tickets = nullptr;
+  uint32_t *d_streams = nullptr, *d_hist = nullptr, *d_counts = nullptr, *d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nb_max * 4)) || (rc = dev.array(&d_streams, nb_max)) || (rc = dev.array(&d_bin, nb_max * 2)) ||
+      (rc = dev.array(&d_carry, nb_max * L * INFLX_PD_CARRY_DOUBLES)) || (rc = dev.array(&d_words, nb_max * L * INFLX_PD_CARRY_WORDS)) ||
+      (rc = dev.array(&d_tickets, nb_max)) || (rc = dev.array(&d_hist, nb_max * row)) || (rc = dev.array(&d_counts, nb_max * INFLX_PD_STATUSES)) ||
+      (rc = dev.array(&d_running, 1)))
+    return rc;
+  std::vector<uint32_t> host_streams(nb_max);
+  std::vector<double> host_bin(nb_max * 2);
+  // Launches of a pass.  A unit is an accepted step or a fresh start, a realisation takes at most max_steps + 1 of them, and a lane
+  // that is not retired uses all 256 of a launch.  Until the launch that draws the last ticket below R all min(L, R) lanes of a point
+  // do, which makes at most ceil(R / min(L, R)) (ceil(max_steps / 256) + 1) + 1 launches; then every lane finishes the realisation
+  // it holds, ceil(max_steps / 256) + 1 launches, and retires in the next at the latest.
+  const uint64_t first_lanes = std::min<uint64_t>(L, R), per_lane = ((uint64_t)R + first_lanes - 1) / first_lanes + 1;
+  const uint64_t windows = ((uint64_t)max_steps + INFLX_BG_STEPS_PER_LAUNCH - 1) / INFLX_BG_STEPS_PER_LAUNCH + 1;
+  const uint64_t launch_limit = per_lane > (UINT64_MAX - 2) / windows ? UINT64_MAX : per_lane * windows + 2;
+
+  for (size_t c0 = 0; c0 < B; c0 += nb_max) {
+    const size_t nb = std::min(nb_max, B - c0), lanes = nb * L;
+    for (size_t b = 0; b < nb; ++b) {
+      host_streams[b] = streams ? streams[c0 + b] : (uint32_t)(c0 + b);
+      const double* r = ranges + (n_ranges == 1 ? 0 : 2 * (c0 + b));
+      host_bin[2 * b] = r[0];
+      host_bin[2 * b + 1] = (double)bins / (r[1] - r[0]);
+    }
+    InflxPdArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = d_init;
+    a.streams = d_streams;
+    a.bin = d_bin;
+    a.carry = d_carry;
+    a.words = d_words;
+    a.tickets = d_tickets;
+    a.hist = d_hist;
+    a.counts = d_counts;
+    a.running = d_running;
+    a.nb = nb;
+    a.seed = seed;
+    a.first = first_realisation;
+    a.max_steps = max_steps;
+    a.R = (uint32_t)R;
+    a.L = (uint32_t)L;
+    a.bins = (uint32_t)bins;
+    a.steps = INFLX_BG_STEPS_PER_LAUNCH;
+    a.noise_scale = noise_scale;
+    a.dn_max = dN_max;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    void* params[] = {&a};
+    const unsigned grid = (unsigned)((lanes + INFLX_PD_THREADS - 1) / INFLX_PD_THREADS);
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, nb * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_streams, host_streams.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_bin, host_bin.data(), nb * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_hist, 0, nb * row * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(d_counts, 0, nb * INFLX_PD_STATUSES * sizeof(uint32_t), s));
+    HIP_TRY(hipModuleLaunchKernel(pd.fn[kPdInit], grid, 1, 1, INFLX_PD_THREADS, 1, 1, 0, s, params, nullptr));
+    for (uint64_t launch = 0;; ++launch) {
+      if (launch >= launch_limit) {
+        (void)hipStreamSynchronize(s);
+        return fail(INFLX_ERR_DEVICE, "internal: lanes of the first-passage histograms still run after %llu launches, more than the arguments allow",
+                    (unsigned long long)launch);
+      }
+      uint32_t running = 0;
+      HIP_TRY(hipMemsetAsync(d_running, 0, sizeof(uint32_t), s));
+      HIP_TRY(hipModuleLaunchKernel(pd.fn[kPdAdvance + mi], grid, 1, 1, INFLX_PD_THREADS, 1, 1, 0, s, params, nullptr));
+      HIP_TRY(hipMemcpyAsync(&running, d_running, sizeof running, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      if (running == 0) break;
+    }
+    HIP_TRY(hipMemcpyAsync(hist + c0 * row, d_hist, nb * row * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(counts + c0 * INFLX_PD_STATUSES, d_counts, nb * INFLX_PD_STATUSES * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
   return sf_verdict(m);
 }
