@@ -678,5 +678,7 @@ int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p
 #include "inflx_hip_stochastic.h"
 /* first-passage histograms (the distribution of N over realisations on lanes that are used again): likewise */
 #include "inflx_hip_distribution.h"
+/* horizon crossings (the state where ln(a H) reaches given values, the located end of inflation): likewise */
+#include "inflx_hip_crossing.h"
 
 #endif /* INFLX_HIP_H */

@@ -165,6 +165,18 @@ DISTRIBUTION_SIGNATURES = {
          C.c_double, _SIZE, _DP, _SIZE, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     ),
 }
+# ... and for include/inflx_hip_crossing.h
+CROSSING_SIGNATURES = {
+    "inflx_solve_eom_crossings": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _DP, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, C.c_uint, _DP, _DP, C.POINTER(C.c_int8),
+         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    ),
+    "inflx_inflation_end": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, _DP, _DP, _DP, C.POINTER(C.c_int8)],
+    ),
+}
 PD_MAX_REALISATIONS = (1 << 32) - 1
 PD_MAX_BINS = 1 << 20
 PD_MAX_LANES_PER_POINT = 1 << 20
@@ -188,7 +200,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h"), os.path.join(_PKG, "csrc", "inflx_stochastic_abi.h"), os.path.join(_REPO, "include", "inflx_hip_stochastic.h"), os.path.join(_PKG, "csrc", "inflx_distribution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_distribution.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h"), os.path.join(_PKG, "csrc", "inflx_stochastic_abi.h"), os.path.join(_REPO, "include", "inflx_hip_stochastic.h"), os.path.join(_PKG, "csrc", "inflx_distribution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_distribution.h"), os.path.join(_PKG, "csrc", "inflx_crossing_abi.h"), os.path.join(_REPO, "include", "inflx_hip_crossing.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -245,7 +257,7 @@ def load_library():
         _preload_hip_runtime()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items(), *EVOLUTION_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items(),
-                                  *DISTRIBUTION_SIGNATURES.items()):
+                                  *DISTRIBUTION_SIGNATURES.items(), *CROSSING_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -591,6 +603,55 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return out, efolds, status, n_stored
+
+    # ---- horizon crossings (include/inflx_hip_crossing.h: inflx_solve_eom_crossings, inflx_inflation_end) ------
+    def solve_eom_crossings(self, p, init, offset, samples, max_steps: int, method: int, max_err: float, dt: float, flags: int):
+        """B trajectories from ``init`` (B,4), each at the crossings ln(a H) = ``offset`` (B,) + ``samples`` (S,).  Returns (out (S, 8,
+        B): y[0..5], t, epsilon_H at every crossing, trajectory fastest; efolds; status (int8); n_stored (uint32); n_before (uint32)).
+        ``flags``: ``EOM_STOP_AT_END`` or 0.  The crossing object must be in place (``CompilationArtifact.ensure_crossing``)."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        samples = _f64(samples, "samples")
+        offset = _f64(offset, "offset")
+        if samples.ndim != 1:
+            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        B, S = init.shape[0], samples.size
+        if offset.shape != (B,):
+            raise InflatoxShapeError(f"offset must have shape ({B},) (got {offset.shape})")
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        out = np.empty((S, 8, B))
+        efolds = np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        n_stored = np.empty(B, dtype=np.uint32)
+        n_before = np.empty(B, dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        _check(
+            self._lib.inflx_solve_eom_crossings(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, _ptr(offset), _ptr(samples), S, int(max_steps), int(method), float(max_err), float(dt),
+                int(flags), _ptr(out), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)), n_stored.ctypes.data_as(u32), n_before.ctypes.data_as(u32),
+            )
+        )  # fmt: skip
+        return out, efolds, status, n_stored, n_before
+
+    def inflation_end(self, p, init, max_steps: int, method: int, max_err: float, dt: float):
+        """B trajectories from ``init`` (B,4) to the end of inflation, located on the dense output.  Returns (states (B, 6), t, eps_h,
+        status (int8)): where every trajectory stopped -- the located end state for status ``INFLX_EOM_ENDED``."""
+        init = _f64(init, "init")
+        p = _f64(p, "p")
+        B = init.shape[0]
+        P = 1 if p.ndim <= 1 else p.shape[0]
+        p = p.reshape(-1)
+        states = np.empty((B, 6))
+        t, eps_h = np.empty(B), np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        _check(
+            self._lib.inflx_inflation_end(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(max_steps), int(method), float(max_err), float(dt), _ptr(states), _ptr(t), _ptr(eps_h),
+                status.ctypes.data_as(C.POINTER(C.c_int8)),
+            )
+        )  # fmt: skip
+        return states, t, eps_h, status
 
     # ---- trajectory kinematics (include/inflx_hip.h: inflx_kinematics) --------------------------
     def kinematics(self, p, states: np.ndarray, n: int, ld: int, traj_len: int = 1) -> np.ndarray:

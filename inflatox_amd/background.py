@@ -34,7 +34,13 @@ input of the stochastic delta-N formalism; ``stochastic_map`` places the points 
 distribution P(N) itself, a histogram per point over up to 2^32 - 1 realisations run on GPU lanes that are used again as realisations
 finish, and ``stochastic_distribution_map`` places the points on a sweep grid; ``distribution_pdf``, ``distribution_survival``,
 ``distribution_mean`` and ``distribution_tail_rate`` read a density, the survival function, the mean and the rate of an exponential
-tail off such a histogram on the host.
+tail off such a histogram on the host.  ``horizon_crossings`` returns every trajectory's state where the comoving Hubble scale
+ln(a H) reaches the points of one list of wavenumbers shared by all of them, located inside the accepted step like ``state_at_efolds``
+locates N, and ``inflation_end`` the state where epsilon_H = 1 on the same dense output.  On top of them ``power_spectra_at_k``,
+``tensor_spectra_at_k`` and ``observables_at_k`` are ``power_spectra``, ``tensor_spectra`` and ``observables`` on a k-grid common to all
+trajectories; ``reheating_offset`` turns a physical wavenumber today and a reheating history into the offset of that grid, and
+``pivot_exit_map`` and ``pivot_observables_map`` draw the exit state, N_star, n_s and r of such a pivot scale over a sweep grid, N_star
+following from every trajectory instead of being guessed.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -63,7 +69,9 @@ __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map
            "TransferSolution", "power_spectra", "spectrum_map", "PowerSpectra", "tensor_spectra", "TensorSpectra", "observables", "Observables", "observables_map",
            "delta_N", "DeltaN", "fnl_map", "delta_N_status", "spectra_evolution", "SpectraEvolution", "evolution_map", "transfer_from_spectra",
            "stochastic_efolds", "stochastic_map", "StochasticEfolds", "stochastic_distribution", "stochastic_distribution_map", "StochasticDistribution",
-           "distribution_pdf", "distribution_survival", "distribution_mean", "distribution_tail_rate"]  # fmt: skip
+           "distribution_pdf", "distribution_survival", "distribution_mean", "distribution_tail_rate", "horizon_crossings", "CrossingSolution", "inflation_end",
+           "InflationEnd", "power_spectra_at_k", "tensor_spectra_at_k", "ExitPoints", "observables_at_k", "reheating_offset", "pivot_exit_map",
+           "pivot_observables_map", "OUTSIDE_AT_START"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -1812,3 +1820,429 @@ def distribution_tail_rate(d: StochasticDistribution, N_from):
             err[b] = rate[b] / math.sqrt(n_in)
     shape = np.shape(d.n_ended)
     return rate.reshape(shape), err.reshape(shape)
+
+
+# ---- horizon crossings: states at given comoving wavenumbers, the pivot scale ------------------------------------------------------
+#: ``power_spectra_at_k``, ``tensor_spectra_at_k`` and ``observables_at_k`` only (no kernel status): the mode was outside the horizon
+#: at the trajectory's start, or left it fewer than ``N_sub`` e-folds after the start
+OUTSIDE_AT_START = 9
+STATUS[OUTSIDE_AT_START] = "the mode was outside the horizon at the start, or left it fewer than N_sub e-folds later (power_spectra_at_k)"
+
+#: the constants of ``reheating_offset``: 1 / Mpc = hbar c / Mpc and 1 K = k_B K in GeV (CODATA 2018, IAU 2015: 6.39493e-39 and
+#: 8.617333e-14), the CMB temperature today in K, the entropy degrees of freedom today
+MPC_INV_GEV = 1.973269804e-16 / 3.0856775814913673e22
+KELVIN_GEV = 8.617333262e-14
+T_CMB_K = 2.7255
+GS_TODAY = 43.0 / 11.0
+
+
+class CrossingSolution(NamedTuple):
+    """What :func:`horizon_crossings` returns, for B trajectories and S wavenumbers.  ``states`` (B, S, 5): phi^0, phi^1, chi^0, chi^1,
+    H where ln(a H) reaches ``offset + ln_k[j]``; ``N``, ``t`` and ``eps_H`` (B, S): e-folds, cosmic time and epsilon_H there -- views
+    of one (S, 8, B) array, trajectory fastest; ``ln_aH`` (B, S): N + ln H of the located state, the target up to the residual of the
+    root search; all five are NaN for a crossing that was not emitted.  ``n_before`` (B,): the targets below ln H_0, whose modes were
+    outside the horizon before the start; ``n_stored`` (B,): the crossings emitted, always j = ``n_before`` .. ``n_before + n_stored
+    - 1``; ``N_end`` (B,): N at epsilon_H = 1 of a trajectory that ENDED (``stop_at_end``; ``efolds_map``'s linear rule), NaN
+    otherwise; ``status`` (B,) int8: ``TARGET`` when every crossing at or after the start was emitted."""
+
+    states: np.ndarray
+    N: np.ndarray
+    t: np.ndarray
+    eps_H: np.ndarray
+    ln_aH: np.ndarray
+    n_stored: np.ndarray
+    n_before: np.ndarray
+    N_end: np.ndarray
+    status: np.ndarray
+
+
+class InflationEnd(NamedTuple):
+    """What :func:`inflation_end` returns.  ``state`` (B, 5): phi^0, phi^1, chi^0, chi^1, H where epsilon_H = 1 on the dense output;
+    ``N_end``, ``t_end`` and ``eps_H`` (B,): e-folds, cosmic time and epsilon_H there (1 up to the root search's bracket) -- all NaN
+    unless ``status`` (B,) int8 is ``ENDED``."""
+
+    state: np.ndarray
+    N_end: np.ndarray
+    t_end: np.ndarray
+    eps_H: np.ndarray
+    status: np.ndarray
+
+
+class ExitPoints(NamedTuple):
+    """The second value of :func:`power_spectra_at_k` and :func:`tensor_spectra_at_k`: ``ln_k`` (K,) as requested (without the
+    offset) and ``N_exit`` (B, K), the e-fold count at which every trajectory's ln(a H) crosses it -- NaN where it does not."""
+
+    ln_k: np.ndarray
+    N_exit: np.ndarray
+
+
+def _check_ln_k(ln_k):
+    try:
+        pts = np.ascontiguousarray(ln_k, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("ln_k must be convertible to a float64 array") from None
+    if pts.ndim != 1:
+        raise InflatoxShapeError(f"ln_k must be one-dimensional (got shape {pts.shape})")
+    if pts.size < 1 or pts.size >= 2**32:
+        raise ValueError(f"the number of wavenumbers must be in [1, 2^32) (got {pts.size})")
+    if not np.isfinite(pts).all():
+        raise ValueError("ln_k must be finite")
+    if not (np.diff(pts) > 0.0).all():
+        raise ValueError("ln_k must be strictly increasing")
+    return pts
+
+
+def _check_offset(offset, B):
+    if offset is None:
+        return np.zeros(B)
+    try:
+        off = np.asarray(offset, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("offset must be None, a number or an array of numbers") from None
+    if off.ndim == 0:
+        off = np.full(B, float(off))
+    if off.shape != (B,):
+        raise InflatoxShapeError(f"offset must be None, a scalar or have shape ({B},) (got {off.shape})")
+    if not np.isfinite(off).all():
+        raise ValueError("offset must be finite")
+    return np.ascontiguousarray(off)
+
+
+def _check_fields(fields_init, derivatives_init):
+    x = np.ascontiguousarray(fields_init, dtype=np.float64)
+    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
+        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    return x, v
+
+
+def _crossing_dylib(artifact):
+    artifact.ensure_crossing()
+    return _dylib(artifact, background=False)
+
+
+def horizon_crossings(artifact: CompilationArtifact, pars, ln_k, fields_init, derivatives_init, *, offset=None, max_steps: int = 100_000,
+                      max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None, stop_at_end: bool = True) -> CrossingSolution:  # fmt: skip
+    """The state of B trajectories where the comoving Hubble scale ln(a H) = N + ln H reaches every point of ``ln_k`` (S,), one list
+    shared by all of them: the horizon exits of the comoving wavenumbers k = e^ln_k, in the solver's own units -- 3 H^2 = rho, reduced
+    Planck mass 1, a = 1 at the trajectory's start, so that ln(a H) starts at ln H_0.  ``ln_k`` is finite and strictly increasing and
+    may be negative; ``offset`` (None, a scalar or (B,)) is added to it per trajectory: the targets of trajectory b are
+    ``offset[b] + ln_k[j]``.  The other arguments are ``solve_eom_sampled``'s, and so are the steps: a trajectory goes on from every
+    accepted step's end state.
+
+    Crossing j is emitted from the first accepted step whose end state has ln(a H) >= its target, at the theta in (0, 1] where the
+    cubic Hermite interpolants of N and H over the step (``state_at_efolds``' dense output) have N(theta) + ln H(theta) = target:
+    Newton's iteration inside a bracket that every iterate tightens, an iterate that leaves the bracket or is not finite replaced by
+    the midpoint, at most 64 iterations, stopping at 1e-15 in theta.  All components come from the interpolant at theta, epsilon_H from
+    the model there; neither N nor H is overwritten, so ``ln_aH`` differs from the target by what the stopping rule leaves.  A target
+    below ln H_0 is not emitted -- the mode was outside the horizon before the start -- and counted in ``n_before``; one equal to it
+    is the initial state.  With ``stop_at_end`` the step that ends inflation emits only the crossings whose N is <= ``N_end``; without
+    it ln(a H) may fall again, and the first step whose end state reaches the target still defines the crossing.  ``status`` is
+    ``TARGET`` once every crossing at or after the start is emitted, ``ENDED`` or ``COMPLETE`` otherwise, ``NONFINITE`` for a located
+    state that is not finite.  The kernels are built into ``<artefact>.crossing`` on first use
+    (``CompilationArtifact.ensure_crossing``).  Bad arguments raise before anything runs on the device."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    pts = _check_ln_k(ln_k)
+    x, v = _check_fields(fields_init, derivatives_init)
+    B = x.shape[0]
+    off = _check_offset(offset, B)
+    p = _pars(artifact, pars, B)
+    init = np.concatenate([x, v], axis=1)
+    flags = _native.EOM_STOP_AT_END if stop_at_end else 0
+    out, n_end, status, n_stored, n_before = _crossing_dylib(artifact).solve_eom_crossings(p, init, off, pts, max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ln_ah = out[:, 5].T + np.log(out[:, 4].T)
+    return CrossingSolution(out[:, :5].transpose(2, 0, 1), out[:, 5].T, out[:, 6].T, out[:, 7].T, ln_ah, n_stored, n_before,
+                            np.where(status == ENDED, n_end, np.nan), status)  # fmt: skip
+
+
+def inflation_end(artifact: CompilationArtifact, pars, fields_init, derivatives_init, *, max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf",
+                  dt: float | None = None) -> InflationEnd:  # fmt: skip
+    """The end of inflation of B trajectories as a state: a trajectory stops in the first accepted step whose end state has
+    epsilon_H >= 1, and the point where epsilon_H = 1 is located on that step's cubic Hermite interpolant by the Illinois iteration that
+    ``delta_N``'s centres use, epsilon_H evaluated through the model at every iterate.  The whole located state is returned, so H_end
+    and N_end are read off the same point.  This ``N_end`` is accurate to the dense output's order; ``efolds_map``'s and
+    ``solve_eom_sampled``'s are linear in epsilon_H across the step, and the two differ at second order in the step (nothing is pinned
+    between them).  A trajectory that starts at or past the end ends at its initial state, ``N_end`` = 0.  ``status`` is ``ENDED`` where
+    the end was found and ``COMPLETE`` where ``max_steps`` accepted steps ran out first.  The kernels are those of
+    ``<artefact>.crossing``.  Bad arguments raise before anything runs on the device."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    x, v = _check_fields(fields_init, derivatives_init)
+    p = _pars(artifact, pars, x.shape[0])
+    init = np.concatenate([x, v], axis=1)
+    states, t, eps, status = _crossing_dylib(artifact).inflation_end(p, init, max_steps, _METHODS[solver], max_err, dt or 0.0)
+    hit = status == ENDED
+    states = np.where(hit[:, None], states, np.nan)
+    return InflationEnd(states[:, :5], states[:, 5], np.where(hit, t, np.nan), np.where(hit, eps, np.nan), status)
+
+
+def _check_at_k(artifact, pars, ln_k, fields_init, derivatives_init, offset, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end):
+    """The argument checks of the ``*_at_k`` calls: (p, ln_k (K,), x, v (B, 2), offset (B,), N_eval, N_sub, max_steps, max_err, dt)."""
+    max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
+    pts = _check_ln_k(ln_k)
+    N_sub = _check_n_sub(N_sub)
+    if N_eval is None:
+        if not stop_at_end:
+            raise ValueError("N_eval=None evaluates at the end of inflation and needs stop_at_end")
+    else:
+        try:
+            N_eval = float(N_eval)
+        except (TypeError, ValueError):
+            raise ValueError("N_eval must be None or a number") from None
+        if not (math.isfinite(N_eval) and N_eval > N_sub):
+            raise ValueError(f"N_eval must be finite and > N_sub = {N_sub} (got {N_eval})")
+    x, v = _check_fields(fields_init, derivatives_init)
+    off = _check_offset(offset, x.shape[0])
+    p = _pars(artifact, pars, x.shape[0])
+    return p, pts, x, v, off, N_eval, N_sub, max_steps, max_err, dt
+
+
+def _mode_lanes_at_k(artifact, tensor, p, pts, x, v, off, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end):
+    """``_mode_lanes`` with every trajectory's own exits: (out (planes, B K), h_exit (B, K), n_exit (B, K), lane_start (B K,),
+    n_end (B K,), status (B K,))."""
+    B, K = x.shape[0], pts.size
+    cr = horizon_crossings(artifact, p, pts, x, v, offset=off, max_steps=max_steps, max_err=max_err, solver=solver, dt=dt, stop_at_end=stop_at_end)
+    n_exit = np.array(cr.N)
+    with np.errstate(invalid="ignore"):
+        inside = np.isfinite(n_exit) & (n_exit >= N_sub)
+        if N_eval is not None and (n_exit[inside] >= N_eval).any():
+            raise ValueError(f"N_eval must be > every located N_exit (the largest is {n_exit[inside].max()}, N_eval = {N_eval})")
+    # a crossing that was not emitted keeps its trajectory's status, unless the mode was outside at the start (or too close to it)
+    emitted = np.arange(K)[None, :] >= cr.n_before[:, None]
+    status = np.where(emitted & ~np.isfinite(n_exit), cr.status[:, None], OUTSIDE_AT_START).astype(np.int8).reshape(-1)
+    lanes = np.flatnonzero(inside.reshape(-1))
+    b_of = lanes // K
+    exits = n_exit.reshape(-1)[lanes]
+    starts = exits - N_sub
+    lane_start = np.full(B * K, np.nan)
+    lane_start[lanes] = starts
+    h_exit = np.full(B * K, np.nan)
+    out = np.full((8 if tensor else 22, B * K), np.nan)
+    n_end = np.full(B * K, np.nan)
+    if lanes.size:
+        rows = p if p.ndim == 1 else p[b_of]
+        n = lanes.size
+        both = state_at_efolds(artifact, rows if p.ndim == 1 else np.concatenate([rows, rows]), np.concatenate([x[b_of], x[b_of]]), np.concatenate([v[b_of], v[b_of]]),
+                               np.concatenate([starts, exits]), max_steps, max_err, solver, dt=dt, stop_at_end=stop_at_end)  # fmt: skip
+        start, h = both.state[:n, :4], both.state[n:, 4]
+        h_exit[lanes] = h
+        found = np.isfinite(start).all(axis=1) & np.isfinite(h)
+        status[lanes] = np.where(found, TARGET, np.where(both.status[:n] != TARGET, both.status[:n], both.status[n:]))
+        run = lanes[found]
+        if run.size:
+            if tensor:
+                artifact.ensure_tensor()
+            else:
+                artifact.ensure_modes()
+            lib = _dylib(artifact, background=False)
+            flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.MODES_TENSOR if tensor else 0)
+            target = np.full(run.size, np.nan) if N_eval is None else N_eval - lane_start[run]
+            kappa = h[found] * math.exp(N_sub)
+            lane_p = p if p.ndim == 1 else np.ascontiguousarray(rows[found])
+            got, ends, st = lib.mode_spectra(lane_p, np.ascontiguousarray(start[found]), np.ascontiguousarray(kappa), target, max_steps, _METHODS[solver], max_err,
+                                             dt or 0.0, flags)  # fmt: skip
+            _mode_stage2_result(out, n_end, status, run, N_eval, got, ends, st)
+    return out, h_exit.reshape(B, K), n_exit, lane_start, n_end, status
+
+
+def _spectra_at_k(artifact, tensor, pars, ln_k, fields_init, derivatives_init, offset, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end):
+    p, pts, x, v, off, N_eval, N_sub, max_steps, max_err, dt = _check_at_k(artifact, pars, ln_k, fields_init, derivatives_init, offset, N_eval, N_sub, max_steps,
+                                                                           max_err, solver, dt, stop_at_end)  # fmt: skip
+    out, h_exit, n_exit, lane_start, n_end, status = _mode_lanes_at_k(artifact, tensor, p, pts, x, v, off, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
+    B, K = h_exit.shape
+    shift = lane_start.reshape(B, K)
+    with np.errstate(invalid="ignore"):
+        k = h_exit * np.exp(n_exit)
+    status = status.reshape(B, K)
+    if tensor:
+        out = out.reshape(8, B, K)
+        res = TensorSpectra(out[0], k, out[5] + shift, out[7], out[1] + 1j * out[2], n_end.reshape(B, K) + shift, status)
+    else:
+        out = out.reshape(22, B, K)
+        q = out[3:11].reshape(2, 2, 2, B, K)  # [I][J][re, im]
+        modes = np.moveaxis(q[:, :, 0] + 1j * q[:, :, 1], (0, 1), (2, 3))
+        res = PowerSpectra(out[0], out[1], out[2], k, out[19] + shift, out[21], modes, n_end.reshape(B, K) + shift, status)
+    return res, ExitPoints(pts, n_exit)
+
+
+def power_spectra_at_k(artifact: CompilationArtifact, pars, ln_k, fields_init, derivatives_init, *, offset=None, N_eval=None, N_sub: float = 5.0,
+                       max_steps: int = 1_000_000, max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None, stop_at_end: bool = True):  # fmt: skip
+    """``power_spectra`` on a grid of comoving wavenumbers that all trajectories share: ``(spectra, exits)`` with ``spectra`` the
+    :class:`PowerSpectra` of (B, K) arrays and ``exits`` the :class:`ExitPoints` -- the requested ``ln_k`` and the located ``N_exit``
+    (B, K).  Row b is DEFINED as ``power_spectra`` of trajectory b alone with ``N_exit`` = the e-fold counts at which its own ln(a H)
+    crosses ``offset[b] + ln_k`` -- bit for bit, in every member; ``k`` is as computed, H_exit e^N_exit, and equals
+    e^(offset + ln_k) up to the crossing's residual.
+
+    ``horizon_crossings`` runs first (``ln_k``, ``offset`` and the units as documented there).  Then every mode's start state at
+    N_exit - ``N_sub`` and its H at N_exit are taken from ``state_at_efolds`` lanes with per-lane targets, which is what
+    ``solve_eom_sampled`` gives ``power_spectra``'s stage 1; then ``power_spectra``'s stage 2 runs unchanged.  A lane whose mode was
+    outside the horizon at the start, or has N_exit < ``N_sub``, gets the status ``OUTSIDE_AT_START`` (a code of this module; no kernel
+    returns it) and NaN values; a crossing the trajectory never reached keeps ``horizon_crossings``' status.  ``N_eval``: None, or an
+    e-fold count since the start, which must be > ``N_sub`` (checked before the device is touched) and above every located N_exit
+    (checked once they are known).  Every other argument is ``power_spectra``'s."""
+    return _spectra_at_k(artifact, False, pars, ln_k, fields_init, derivatives_init, offset, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
+
+
+def tensor_spectra_at_k(artifact: CompilationArtifact, pars, ln_k, fields_init, derivatives_init, *, offset=None, N_eval=None, N_sub: float = 5.0,
+                        max_steps: int = 1_000_000, max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None, stop_at_end: bool = True):  # fmt: skip
+    """``tensor_spectra`` on a grid of comoving wavenumbers that all trajectories share: ``power_spectra_at_k``'s tensor twin, with the
+    same arguments, checks, crossings and ``(spectra, exits)`` -- ``spectra`` a :class:`TensorSpectra`, ``k`` and ``exits``
+    ``power_spectra_at_k``'s bit for bit."""
+    return _spectra_at_k(artifact, True, pars, ln_k, fields_init, derivatives_init, offset, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)
+
+
+def _check_dlnk(dlnk):
+    try:
+        dlnk = float(dlnk)
+    except (TypeError, ValueError):
+        raise ValueError("dlnk must be a number") from None
+    if not (math.isfinite(dlnk) and dlnk > 0.0):
+        raise ValueError(f"dlnk must be finite and > 0 (got {dlnk})")
+    return dlnk
+
+
+def _observables_at_k(artifact, pars, ln_k, fields_init, derivatives_init, dlnk, offset, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end):
+    """``observables_at_k`` and the pivots' located N_exit (B, K)"""
+    dlnk = _check_dlnk(dlnk)
+    pivots = _check_ln_k(ln_k)
+    pts, inverse = np.unique(np.concatenate([pivots - dlnk, pivots, pivots + dlnk]), return_inverse=True)
+    kw = dict(offset=offset, N_eval=N_eval, N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver, dt=dt, stop_at_end=stop_at_end)
+    scalar, exits = power_spectra_at_k(artifact, pars, pts, fields_init, derivatives_init, **kw)
+    tensor, _ = tensor_spectra_at_k(artifact, pars, pts, fields_init, derivatives_init, **kw)
+    cols = inverse.reshape(3, pivots.size)
+    return observables_from_spectra(scalar, tensor, cols, ENDED if N_eval is None else TARGET), exits.N_exit[:, cols[1]]
+
+
+def observables_at_k(artifact: CompilationArtifact, pars, ln_k, fields_init, derivatives_init, *, dlnk: float = 0.5, offset=None, N_eval=None,
+                     N_sub: float = 5.0, max_steps: int = 1_000_000, max_err: float = 1e-8, solver: str = "rkf", dt: float | None = None,
+                     stop_at_end: bool = True) -> Observables:  # fmt: skip
+    """``observables`` at K pivot wavenumbers ``ln_k`` that all trajectories share: ``power_spectra_at_k`` and ``tensor_spectra_at_k``
+    on the sorted, de-duplicated union of ``ln_k - dlnk``, ``ln_k`` and ``ln_k + dlnk``, then ``observables_from_spectra``.  The
+    stencil is uniform in ln k up to the crossings' residual (``log_slopes`` still takes every trajectory's ``k`` as computed), and
+    the derivative is taken at fixed comoving k, not at a fixed e-fold count: n_s, alpha_s and n_t of two trajectories refer to the
+    same scales.  ``dlnk`` must be finite and > 0; the other arguments are ``power_spectra_at_k``'s.  A pivot any of whose six lanes was
+    outside the horizon at the start has the status ``OUTSIDE_AT_START`` and NaN values."""
+    return _observables_at_k(artifact, pars, ln_k, fields_init, derivatives_init, dlnk, offset, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end)[0]
+
+
+def reheating_offset(k_mpc: float = 0.05, *, w_reh: float = 1.0 / 3.0, N_reh: float = 0.0, g_reh: float = 106.75, gs_reh: float = 106.75) -> float:
+    """The constant A of the pivot matching: a mode of physical wavenumber ``k_mpc`` (in 1 / Mpc) today left the horizon where
+
+        ln(a H) = N_end + ln(H_end) / 2 + A,
+        A = ln(k / T_0) + ln(3) / 4 + ln(30 / (pi^2 g_reh)) / 4 + ln(gs_reh / gs_0) / 3 + (1 - 3 w_reh) N_reh / 4
+
+    in the solver's units (3 H^2 = rho, reduced Planck mass 1, a = 1 at the trajectory's start): entropy is conserved after
+    reheating, rho_end = 3 H_end^2, and reheating lasts ``N_reh`` e-folds with the equation of state ``w_reh`` before the plasma of
+    ``g_reh`` energy and ``gs_reh`` entropy degrees of freedom is thermal.  T_0 = 2.7255 K, gs_0 = 43 / 11, 1 / Mpc = 6.39493e-39 GeV
+    and 1 K = 8.617333e-14 GeV; the Planck mass cancels in k / T_0 and enters through H only.  The defaults -- 0.05 / Mpc, 106.75
+    degrees of freedom, instant reheating -- give A = -61.37.  A pure function: ``k_mpc``, ``g_reh`` and ``gs_reh`` must be finite
+    and > 0, ``N_reh`` finite and >= 0, -1/3 < ``w_reh`` <= 1."""
+    try:
+        k_mpc, w_reh, N_reh, g_reh, gs_reh = float(k_mpc), float(w_reh), float(N_reh), float(g_reh), float(gs_reh)
+    except (TypeError, ValueError):
+        raise ValueError("reheating_offset takes numbers") from None
+    for name, value in (("k_mpc", k_mpc), ("g_reh", g_reh), ("gs_reh", gs_reh)):
+        if not (math.isfinite(value) and value > 0.0):
+            raise ValueError(f"{name} must be finite and > 0 (got {value})")
+    if not (math.isfinite(N_reh) and N_reh >= 0.0):
+        raise ValueError(f"N_reh must be finite and >= 0 (got {N_reh})")
+    if not (-1.0 / 3.0 < w_reh <= 1.0):
+        raise ValueError(f"w_reh must be in (-1/3, 1] (got {w_reh})")
+    return (math.log(k_mpc * MPC_INV_GEV / (T_CMB_K * KELVIN_GEV)) + 0.25 * math.log(3.0) + 0.25 * math.log(30.0 / (math.pi**2 * g_reh))
+            + math.log(gs_reh / GS_TODAY) / 3.0 + 0.25 * (1.0 - 3.0 * w_reh) * N_reh)  # fmt: skip
+
+
+def _check_pivot_grid(artifact, pars, start_stop, N0, N1, A, derivatives_init, max_steps, max_err, solver):
+    """The argument checks of the pivot maps: (p, init (N0 N1, 4), A (N0 N1,), N0, N1, max_steps, max_err)."""
+    max_steps, _, max_err, _ = _check_common(artifact, max_steps, max_err, solver, None)
+    ss = np.asarray(start_stop, dtype=np.float64)
+    if ss.size != 4:
+        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
+    N0, N1 = operator.index(N0), operator.index(N1)
+    if N0 < 1 or N1 < 1:
+        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
+    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
+    if d.size != 2:
+        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
+    try:
+        a = np.asarray(A, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("A must be a number or an (N0, N1) array of numbers") from None
+    if a.ndim != 0 and a.shape != (N0, N1):
+        raise InflatoxShapeError(f"A must be a scalar or have shape ({N0}, {N1}) (got {a.shape})")
+    if not np.isfinite(a).all():
+        raise ValueError("A must be finite")
+    p = _pars(artifact, pars, 1)
+    if p.ndim != 1:
+        raise InflatoxShapeError("the pivot maps take one parameter row")
+    x0, x1 = grid_points(ss, N0, N1)
+    init = np.empty((N0 * N1, 4))
+    init[:, 0] = np.repeat(x0, N1)
+    init[:, 1] = np.tile(x1, N0)
+    init[:, 2:] = d
+    return p, init, np.broadcast_to(a, (N0, N1)).reshape(-1), N0, N1, max_steps, max_err
+
+
+def _pivot_crossing(artifact, p, init, A, ln_k, max_steps, max_err, solver):
+    """``inflation_end`` on the points ``init`` and, on those that ended, the crossing of ln(a H) = N_end + ln(H_end) / 2 + A + ln_k:
+    (end, pivot L (n,), state (n, 5), N (n,), status (n,)) -- NaN where nothing was found."""
+    n = init.shape[0]
+    end = inflation_end(artifact, p, init[:, :2], init[:, 2:], max_steps=max_steps, max_err=max_err, solver=solver)
+    status = end.status.copy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pivot = end.N_end + 0.5 * np.log(end.state[:, 4]) + A
+    state, n_at = np.full((n, 5), np.nan), np.full(n, np.nan)
+    run = np.flatnonzero((end.status == ENDED) & np.isfinite(pivot))
+    if run.size:
+        cr = horizon_crossings(artifact, p, [ln_k], init[run, :2], init[run, 2:], offset=pivot[run], max_steps=max_steps, max_err=max_err, solver=solver)
+        state[run], n_at[run] = cr.states[:, 0], cr.N[:, 0]
+        status[run] = np.where(cr.n_before == 1, ENDED_SHORT, cr.status)
+    return end, pivot, state, n_at, status
+
+
+def pivot_exit_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, A, derivatives_init=(0.0, 0.0), max_steps: int = 100_000,
+                   max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """The state at which a physical pivot scale leaves the horizon, from every point of the (N0, N1) grid of ``efolds_map`` (same
+    arguments): ``(state, N_star, N_end)`` with ``state`` (N0, N1, 5) = phi^0, phi^1, chi^0, chi^1, H where
+
+        ln(a H) = N_end + ln(H_end) / 2 + A,
+
+    ``N_star`` (N0, N1) = N_end - N there -- it follows from the trajectory, N_star = ln H_star - ln(H_end) / 2 - A, and differs from
+    point to point -- and ``N_end`` (N0, N1).  ``A`` (a number, or (N0, N1)) holds the wavenumber and the reheating history:
+    ``reheating_offset``.  Two passes of O(N0 * N1) memory: ``inflation_end`` on the grid, then ``horizon_crossings`` with that offset
+    and ``ln_k = [0]`` on the points that ended.  NaN where nothing was found; ``return_status=True`` adds the (N0, N1) int8 status
+    map: ``TARGET`` where the state was found, ``ENDED_SHORT`` where the pivot was outside the horizon at the start -- inflation from
+    this point is too short for it --, ``ENDED`` where inflation ended before the pivot left (A too large), and ``inflation_end``'s
+    status where inflation did not end."""
+    p, init, a, N0, N1, max_steps, max_err = _check_pivot_grid(artifact, pars, start_stop, N0, N1, A, derivatives_init, max_steps, max_err, solver)
+    end, _, state, n_at, status = _pivot_crossing(artifact, p, init, a, 0.0, max_steps, max_err, solver)
+    out = (state.reshape(N0, N1, 5), (end.N_end - n_at).reshape(N0, N1), end.N_end.reshape(N0, N1))
+    return (*out, status.reshape(N0, N1)) if return_status else out
+
+
+def pivot_observables_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, A, dlnk: float = 0.5, N_sub: float = 5.0,
+                          derivatives_init=(0.0, 0.0), max_steps: int = 100_000, max_err: float = 1e-8, solver: str = "rkf", *, return_status: bool = False):  # fmt: skip
+    """n_s, r and the other :class:`Observables` at a physical pivot scale as (N0, N1) maps: ``(obs, state, N_star, N_end)``.  As in
+    ``pivot_exit_map`` the pivot leaves the horizon where ln(a H) = L_star = N_end + ln(H_end) / 2 + A.  ``state`` (N0, N1, 5) is the
+    crossing of L_star - (``dlnk`` + ``N_sub``): since d ln(a H) / dN = 1 - epsilon_H < 1, it lies at least ``N_sub`` e-folds before the
+    exit of the lowest of the three modes.  From it (H taken again from the Friedmann constraint, as in ``observables_map``)
+    ``observables_at_k`` runs with ``ln_k = [0]`` and ``offset`` = L_star minus the restart's N -- a = 1 at the restart -- to the end of
+    inflation.  ``N_star`` (N0, N1) = N_end minus the pivot's own exit, and ``N_end`` (N0, N1) is ``inflation_end``'s.  NaN where nothing
+    was found; ``obs.status`` and, with ``return_status=True``, a fifth member are the (N0, N1) status map: ``pivot_exit_map``'s for the
+    restart state, with ``observables_at_k``'s status (``ENDED`` where the values are valid) in place of ``TARGET``."""
+    N_sub = _check_n_sub(N_sub)
+    dlnk = _check_dlnk(dlnk)
+    p, init, a, N0, N1, max_steps, max_err = _check_pivot_grid(artifact, pars, start_stop, N0, N1, A, derivatives_init, max_steps, max_err, solver)
+    end, pivot, state, n_at, status = _pivot_crossing(artifact, p, init, a, -(dlnk + N_sub), max_steps, max_err, solver)
+    values = np.full((len(Observables._fields) - 1, N0 * N1), np.nan)
+    n_star = np.full(N0 * N1, np.nan)
+    run = np.flatnonzero(np.isfinite(n_at))
+    if run.size:
+        obs, n_exit = _observables_at_k(artifact, p, [0.0], state[run, :2], state[run, 2:4], dlnk, pivot[run] - n_at[run], None, N_sub, max_steps, max_err, solver,
+                                        None, True)  # fmt: skip
+        values[:, run] = [member[:, 0] for member in obs[:-1]]
+        status[run] = obs.status[:, 0]
+        n_star[run] = end.N_end[run] - (n_at[run] + n_exit[:, 0])
+    status = status.reshape(N0, N1)
+    out = (Observables(*values.reshape(-1, N0, N1), status), state.reshape(N0, N1, 5), n_star.reshape(N0, N1), end.N_end.reshape(N0, N1))
+    return (*out, status) if return_status else out

@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" / "stochastic" / "distribution" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" / "stochastic" / "distribution" / "crossing" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -430,6 +430,16 @@ class CompilationArtifact:
             lambda: [("INFLX_EOM_HEADER", "pd{key}.eom.h", self.eom_header_text()), ("INFLX_NOISE_HEADER", "pd{key}.noise.h", self.noise_header_text())],
         )  # fmt: skip
 
+    def ensure_crossing(self) -> str:
+        """Extension: build the crossing code object of this model -- the kernels of ``inflatox_amd.background.horizon_crossings``
+        and ``inflation_end`` (csrc/inflx_crossing_kernels.hip) -- and return its path, ``shared_object_path + ".crossing"``, where
+        ``libinflx_hip.so`` looks for it.  One hipcc step on first use from the core object's header and options plus the header of
+        the equations of motion, cached as ``<tag>.hx<hash>.hsaco`` (the hash covers the generated header and ``_CROSSING_SOURCES``,
+        code only -- csrc/inflx_background.h and csrc/inflx_deltan.h among them, whose stepper, dense output and end-of-inflation
+        search the kernels run); the object carries the core object's ``MODEL_TAG`` and a layout word of its own (``INFLX_HX_ABI``).
+        Like the other ten companion objects it lies outside the kernel groups, and none of them is involved."""
+        return self._ensure_companion("crossing", _CROSSING_SOURCES, "hx{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "hx{key}.eom.h", self.eom_header_text())])
+
     def ensure_rowpass(self) -> str | None:
         """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
         evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
@@ -563,6 +573,8 @@ _STOCHASTIC_SOURCES = ("inflx_stochastic_kernels.hip", "inflx_stochastic.h", "in
                        "inflx_background_abi.h")  # fmt: skip
 _DISTRIBUTION_SOURCES = ("inflx_distribution_kernels.hip", "inflx_distribution.h", "inflx_distribution_abi.h", "inflx_stochastic.h", "inflx_philox.h",
                          "inflx_background.h", "inflx_background_abi.h")  # fmt: skip
+_CROSSING_SOURCES = ("inflx_crossing_kernels.hip", "inflx_crossing.h", "inflx_crossing_abi.h", "inflx_deltan.h", "inflx_background.h",
+                     "inflx_background_abi.h")  # fmt: skip
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 

@@ -52,6 +52,7 @@
 #include "inflx_evolution_abi.h"
 #include "inflx_stochastic_abi.h"
 #include "inflx_distribution_abi.h"
+#include "inflx_crossing_abi.h"
 
 namespace {
 
@@ -372,7 +373,7 @@ struct TableRing {
 
 // The code objects beside the core object that the background solver's families live in (kCompanions describes them), and what a
 // handle holds of one: its module and its kernels, in the order of the description's names.
-enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kObjStochastic, kObjDistribution, kCompanionCount };
+enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kObjStochastic, kObjDistribution, kObjCrossing, kCompanionCount };
 constexpr int kCompanionKernels = 10;  // the most kernels of one object (background)
 struct CompanionSlot {
   hipModule_t module = nullptr;
@@ -2894,7 +2895,7 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* mm, int op, const double* p, siz
 }  // extern "C"
 
 // ---- the background solver: what its families share ---------------------------------------------------------------------------
-// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution, stochastic e-folds, first-passage histograms -- has its kernels in
+// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution, stochastic e-folds, first-passage histograms, horizon crossings -- has its kernels in
 // a code object of its own beside the core object, `<artefact>.<suffix>`, which CompilationArtifact.ensure_<suffix>() builds.
 // kCompanions has one constant description per object: the words of its messages, its layout word, its kernels.  need_companion
 // loads any of them into its slot of the handle on first use, and a call site names a kernel by its family's index below.  The
@@ -2914,6 +2915,7 @@ static_assert(kAbiMajor == INFLX_DN_DEFAULT_ABI_MAJOR, "a delta-N object reports
 static_assert(kAbiMajor == INFLX_EV_DEFAULT_ABI_MAJOR, "an evolution object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_ST_DEFAULT_ABI_MAJOR, "a stochastic object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_PD_DEFAULT_ABI_MAJOR, "a distribution object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_HX_DEFAULT_ABI_MAJOR, "a crossing object reports the core object's ABI major: change both together");
 
 struct CompanionDesc {
   const char* suffix;      // the file is `<artefact>.<suffix>` and CompilationArtifact.ensure_<suffix>() builds it
@@ -2931,6 +2933,7 @@ enum LaneKernel { kLaneInit, kLaneAdvance /* + method */ };  // transfer, modes,
 enum DnKernel { kDnInit, kDnReduce, kDnEnd /* + method: phase A */, kDnSurface = 4 /* + method: phase B */ };
 enum StKernel { kStInit, kStReduce, kStAdvance /* + method */ };
 enum PdKernel { kPdInit, kPdAdvance /* + method */ };
+enum HxKernel { kHxInit, kHxAdvance /* + method: crossings */, kHxEnd = 3 /* + method: the end of inflation */ };
 const CompanionDesc kCompanions[kCompanionCount] = {
     {"background", "background kernels", "are", "inflatox_amd.background", "INFLX_BG_ABI", INFLX_BG_ABI_VERSION,
      {"inflx_bg_init", "inflx_bg_rows_transpose", "inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows", "inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows",
@@ -2951,6 +2954,8 @@ const CompanionDesc kCompanions[kCompanionCount] = {
      {"inflx_st_init", "inflx_st_reduce", "inflx_st_advance_rk4", "inflx_st_advance_rkf"}},
     {"distribution", "distribution kernels", "are", "inflatox_amd.background.stochastic_distribution", "INFLX_PD_ABI", INFLX_PD_ABI_VERSION,
      {"inflx_pd_init", "inflx_pd_advance_rk4", "inflx_pd_advance_rkf"}},
+    {"crossing", "crossing kernels", "are", "inflatox_amd.background.horizon_crossings", "INFLX_HX_ABI", INFLX_HX_ABI_VERSION,
+     {"inflx_hx_init", "inflx_hx_advance_rk4", "inflx_hx_advance_rkf", "inflx_hx_end_rk4", "inflx_hx_end_rkf"}},
 };
 
 // Load the companion object `which` beside the core object, unless the handle has it: it must carry the core object's VERSION and
@@ -4091,6 +4096,134 @@ int inflx_stochastic_distribution(inflx_model* m, const double* p, size_t P, siz
     HIP_TRY(hipMemcpyAsync(hist + c0 * row, d_hist, nb * row * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(counts + c0 * INFLX_PD_STATUSES, d_counts, nb * INFLX_PD_STATUSES * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+  }
+  return sf_verdict(m);
+}
+
+}  // extern "C"
+
+// ---- horizon crossings: the state where ln(a H) reaches given values, and the located end of inflation (inflx_solve_eom_crossings, inflx_inflation_end) ----
+extern "C" {
+
+int inflx_solve_eom_crossings(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* offset, const double* samples, size_t S,
+                              size_t max_steps, int method, double max_err, double dt, unsigned flags, double* out, double* efolds, int8_t* status, uint32_t* n_stored,
+                              uint32_t* n_before) {
+  INFLX_SERIALISE(m);
+  int rc = check_integrator_args(m, "the horizon crossings require", "trajectory", p, P, n_p, B, method, flags, INFLX_EOM_STOP_AT_END, max_steps, max_err, dt, status);
+  if (rc || (rc = check_samples(samples, S, /*negative=*/true))) return rc;
+  if (offset)
+    for (size_t l = 0; l < B; ++l)
+      if (!std::isfinite(offset[l])) return fail(INFLX_ERR_ARG, "offset %zu is not a finite number", l);
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  if (!out) return fail(INFLX_ERR_ARG, "output array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_companion(m, kObjCrossing))) return rc;
+  hipStream_t s = m->stream;
+  // lanes reach a crossing in different launches, so the device buffer holds all S samples of a pass's lanes
+  const size_t plane_bytes = S * INFLX_HX_SAMPLE_PLANES * sizeof(double);  // (of one lane)
+  const size_t nc_max = inflx_bg_lanes_per_pass(B, plane_bytes, INFLX_HX_THREADS);
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_samples = nullptr, *d_init = nullptr, *d_offset = nullptr, *d_carry = nullptr, *d_out = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_samples, S))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_samples, samples, S * sizeof(double), hipMemcpyHostToDevice, s));
+  if ((rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_offset, nc_max)) || (rc = dev.array(&d_carry, nc_max * INFLX_HX_CARRY_PLANES)) ||
+      (rc = dev.array(&d_out, nc_max * S * INFLX_HX_SAMPLE_PLANES)) || (rc = dev.array(&d_running, 1)))
+    return rc;
+  std::vector<double> host_carry(nc_max * INFLX_HX_CARRY_PLANES);
+  const CompanionSlot& hx = m->companion[kObjCrossing];
+  hipFunction_t advance = hx.fn[kHxAdvance + (method == INFLX_EOM_RKF ? 1 : 0)];
+
+  for (size_t c0 = 0; c0 < B; c0 += nc_max) {
+    const size_t n = std::min(nc_max, B - c0);
+    InflxHxArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = d_init;
+    a.carry = d_carry;
+    a.out = d_out;
+    a.n = n;
+    a.flags = (flags & INFLX_EOM_STOP_AT_END) ? 1u : 0u;
+    a.n_samples = (uint32_t)S;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    a.offset = offset ? d_offset : nullptr;
+    a.samples = d_samples;
+    a.running = d_running;
+    void* params[] = {&a};
+    const unsigned grid = (unsigned)((n + INFLX_HX_THREADS - 1) / INFLX_HX_THREADS);
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (offset) HIP_TRY(hipMemcpyAsync(d_offset, offset + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    // every byte 0xff: each double is a NaN, which a sample that its lane does not emit keeps
+    HIP_TRY(hipMemsetAsync(d_out, 0xff, n * plane_bytes, s));
+    HIP_TRY(hipModuleLaunchKernel(hx.fn[kHxInit], grid, 1, 1, INFLX_HX_THREADS, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(advance, a, grid, INFLX_HX_THREADS, max_steps, s))) return rc;
+    // the planes as they are: plane (sample, component) of this pass's lanes is n doubles, B doubles apart in `out`
+    HIP_TRY(hipMemcpy2DAsync(out + c0, B * sizeof(double), d_out, n * sizeof(double), n * sizeof(double), INFLX_HX_SAMPLE_PLANES * S, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry, n * INFLX_HX_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double* hc = host_carry.data();
+    for (size_t l = 0; l < n; ++l) {
+      status[c0 + l] = (int8_t)hc[INFLX_HX_CARRY_STATUS * n + l];
+      if (efolds) efolds[c0 + l] = hc[INFLX_HX_CARRY_NEND * n + l];
+      const uint32_t before = (uint32_t)hc[INFLX_HX_CARRY_BEFORE * n + l];
+      if (n_before) n_before[c0 + l] = before;
+      if (n_stored) n_stored[c0 + l] = (uint32_t)hc[INFLX_HX_CARRY_CURSOR * n + l] - before;
+    }
+  }
+  return sf_verdict(m);
+}
+
+int inflx_inflation_end(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t max_steps, int method, double max_err, double dt,
+                        double* states, double* t, double* eps_h, int8_t* status) {
+  INFLX_SERIALISE(m);
+  int rc = check_integrator_args(m, "the end of inflation requires", "trajectory", p, P, n_p, B, method, 0, 0, max_steps, max_err, dt, status);
+  if (rc) return rc;
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_companion(m, kObjCrossing))) return rc;
+  hipStream_t s = m->stream;
+  const size_t nc_max = std::min(B, kBgMaxLanes);
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_init = nullptr, *d_carry = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_carry, nc_max * INFLX_HX_CARRY_PLANES)) ||
+      (rc = dev.array(&d_running, 1)))
+    return rc;
+  std::vector<double> host_carry(nc_max * INFLX_HX_CARRY_PLANES);
+  const CompanionSlot& hx = m->companion[kObjCrossing];
+  hipFunction_t advance = hx.fn[kHxEnd + (method == INFLX_EOM_RKF ? 1 : 0)];
+
+  for (size_t c0 = 0; c0 < B; c0 += nc_max) {
+    const size_t n = std::min(nc_max, B - c0);
+    InflxHxArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = d_init;
+    a.carry = d_carry;
+    a.n = n;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    a.running = d_running;
+    void* params[] = {&a};
+    const unsigned grid = (unsigned)((n + INFLX_HX_THREADS - 1) / INFLX_HX_THREADS);
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipModuleLaunchKernel(hx.fn[kHxInit], grid, 1, 1, INFLX_HX_THREADS, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(advance, a, grid, INFLX_HX_THREADS, max_steps, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry, n * INFLX_HX_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double* hc = host_carry.data();
+    for (size_t l = 0; l < n; ++l) {
+      status[c0 + l] = (int8_t)hc[INFLX_HX_CARRY_STATUS * n + l];
+      if (eps_h) eps_h[c0 + l] = hc[INFLX_HX_CARRY_EPS * n + l];
+      if (states)
+        for (int c = 0; c < 6; ++c) states[(c0 + l) * 6 + c] = hc[(size_t)(INFLX_HX_CARRY_Y + c) * n + l];
+      if (t) t[c0 + l] = hc[INFLX_HX_CARRY_T * n + l];
+    }
   }
   return sf_verdict(m);
 }
