@@ -516,10 +516,8 @@ class InflatoxDevLib:
         of shape (B,).  The background object must be in place (``CompilationArtifact.ensure_background``); arguments are checked
         by the caller (inflatox_amd.background) and again by the library."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         B = init.shape[0]
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
         final_only = bool(flags & EOM_FINAL_ONLY)
         states = np.empty((B, 6) if final_only else (B, rows, 6))
         t = np.empty((B,) if final_only else (B, rows))
@@ -529,7 +527,7 @@ class InflatoxDevLib:
         _check(
             self._lib.inflx_solve_eom(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(rows), int(substeps), int(method), float(max_err), float(dt), int(flags),
-                _ptr(states), _ptr(t), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)), last_row.ctypes.data_as(C.POINTER(C.c_int64)),
+                _ptr(states), _ptr(t), _ptr(efolds), _typed(status, C.c_int8), _typed(last_row, C.c_int64),
             )
         )  # fmt: skip
         return states, t, efolds, status, last_row
@@ -541,18 +539,16 @@ class InflatoxDevLib:
         (a hipStream_t as an integer; 0: the handle's stream), which the call synchronises before it returns.  Returns (efolds,
         status (int8), last_row (int64)), host arrays of shape (B,).  ``flags``: ``EOM_STOP_AT_END`` or 0."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         B = init.shape[0]
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
         efolds = np.empty(B)
         status = np.empty(B, dtype=np.int8)
         last_row = np.empty(B, dtype=np.int64)
         _check(
             self._lib.inflx_solve_eom_device(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(rows), int(substeps), int(method), float(max_err), float(dt), int(flags),
-                C.c_void_p(d_states_ptr), int(d_states_bytes), C.c_void_p(d_t_ptr), int(d_t_bytes), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
-                last_row.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(stream),
+                C.c_void_p(d_states_ptr), int(d_states_bytes), C.c_void_p(d_t_ptr), int(d_t_bytes), _ptr(efolds), _typed(status, C.c_int8),
+                _typed(last_row, C.c_int64), C.c_void_p(stream),
             )
         )  # fmt: skip
         return efolds, status, last_row
@@ -562,20 +558,17 @@ class InflatoxDevLib:
         inflx_solve_eom_to_efolds).  Returns (states (B, 6), t, eps_h, efolds, status (int8)): where every trajectory stopped -- the
         located state for status ``INFLX_EOM_TARGET``.  ``flags``: ``EOM_STOP_AT_END`` or 0."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         target = _f64(target, "target")
         B = init.shape[0]
-        if target.shape != (B,):
-            raise InflatoxShapeError(f"target must have shape ({B},) (got {target.shape})")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        _lanes(target, "target", B)
         states = np.empty((B, 6))
         t, eps_h, efolds = np.empty(B), np.empty(B), np.empty(B)
         status = np.empty(B, dtype=np.int8)
         _check(
             self._lib.inflx_solve_eom_to_efolds(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, _ptr(target), int(max_steps), int(method), float(max_err), float(dt), int(flags),
-                _ptr(states), _ptr(t), _ptr(eps_h), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+                _ptr(states), _ptr(t), _ptr(eps_h), _ptr(efolds), _typed(status, C.c_int8),
             )
         )  # fmt: skip
         return states, t, eps_h, efolds, status
@@ -585,13 +578,10 @@ class InflatoxDevLib:
         inflx_solve_eom_sampled).  Returns (out (S, 8, B): y[0..5], t, epsilon_H at every sample, trajectory fastest; efolds; status
         (int8); n_stored (uint32)).  ``flags``: ``EOM_STOP_AT_END``, ``EOM_SAMPLE_T``."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         samples = _f64(samples, "samples")
-        if samples.ndim != 1:
-            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        _one_dimensional(samples)
         B, S = init.shape[0], samples.size
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
         out = np.empty((S, 8, B))
         efolds = np.empty(B)
         status = np.empty(B, dtype=np.int8)
@@ -599,7 +589,7 @@ class InflatoxDevLib:
         _check(
             self._lib.inflx_solve_eom_sampled(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, _ptr(samples), S, int(max_steps), int(method), float(max_err), float(dt), int(flags),
-                _ptr(out), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)), n_stored.ctypes.data_as(C.POINTER(C.c_uint32)),
+                _ptr(out), _ptr(efolds), _typed(status, C.c_int8), _typed(n_stored, C.c_uint32),
             )
         )  # fmt: skip
         return out, efolds, status, n_stored
@@ -610,26 +600,21 @@ class InflatoxDevLib:
         B): y[0..5], t, epsilon_H at every crossing, trajectory fastest; efolds; status (int8); n_stored (uint32); n_before (uint32)).
         ``flags``: ``EOM_STOP_AT_END`` or 0.  The crossing object must be in place (``CompilationArtifact.ensure_crossing``)."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         samples = _f64(samples, "samples")
         offset = _f64(offset, "offset")
-        if samples.ndim != 1:
-            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        _one_dimensional(samples)
         B, S = init.shape[0], samples.size
-        if offset.shape != (B,):
-            raise InflatoxShapeError(f"offset must have shape ({B},) (got {offset.shape})")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        _lanes(offset, "offset", B)
         out = np.empty((S, 8, B))
         efolds = np.empty(B)
         status = np.empty(B, dtype=np.int8)
         n_stored = np.empty(B, dtype=np.uint32)
         n_before = np.empty(B, dtype=np.uint32)
-        u32 = C.POINTER(C.c_uint32)
         _check(
             self._lib.inflx_solve_eom_crossings(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, _ptr(offset), _ptr(samples), S, int(max_steps), int(method), float(max_err), float(dt),
-                int(flags), _ptr(out), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)), n_stored.ctypes.data_as(u32), n_before.ctypes.data_as(u32),
+                int(flags), _ptr(out), _ptr(efolds), _typed(status, C.c_int8), _typed(n_stored, C.c_uint32), _typed(n_before, C.c_uint32),
             )
         )  # fmt: skip
         return out, efolds, status, n_stored, n_before
@@ -638,17 +623,15 @@ class InflatoxDevLib:
         """B trajectories from ``init`` (B,4) to the end of inflation, located on the dense output.  Returns (states (B, 6), t, eps_h,
         status (int8)): where every trajectory stopped -- the located end state for status ``INFLX_EOM_ENDED``."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         B = init.shape[0]
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
         states = np.empty((B, 6))
         t, eps_h = np.empty(B), np.empty(B)
         status = np.empty(B, dtype=np.int8)
         _check(
             self._lib.inflx_inflation_end(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(max_steps), int(method), float(max_err), float(dt), _ptr(states), _ptr(t), _ptr(eps_h),
-                status.ctypes.data_as(C.POINTER(C.c_int8)),
+                _typed(status, C.c_int8),
             )
         )  # fmt: skip
         return states, t, eps_h, status
@@ -660,9 +643,7 @@ class InflatoxDevLib:
         (n / traj_len, n_par), one row per run of ``traj_len`` states.  Returns (6, n): eps_H, eta_par, omega, sigma_dot, V_sigma,
         V_N.  The kinematics object must be in place (``CompilationArtifact.ensure_kinematics``); arguments are checked by the
         caller (inflatox_amd.background) and again by the library."""
-        p = _f64(p, "p")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        p, P = _rows(p)
         out = np.empty((6, n))
         _check(self._lib.inflx_kinematics(self._h, _ptr(p), P, self.n_parameters, _ptr(states), int(n), int(ld), int(traj_len), _ptr(out)))
         return out
@@ -671,9 +652,7 @@ class InflatoxDevLib:
         """``kinematics`` on device arrays (include/inflx_hip.h: inflx_kinematics_device): n states of stride ``ld`` doubles at the
         device address ``d_states_ptr``, the planes (6, n) to ``d_out_ptr``, buffers of the given byte sizes, on ``stream`` (a
         hipStream_t as an integer; 0: the handle's stream), which the call synchronises before it returns."""
-        p = _f64(p, "p")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        p, P = _rows(p)
         _check(
             self._lib.inflx_kinematics_device(
                 self._h, _ptr(p), P, self.n_parameters, C.c_void_p(d_states_ptr), int(d_states_bytes), int(n), int(ld), int(traj_len), C.c_void_p(d_out_ptr),
@@ -685,9 +664,7 @@ class InflatoxDevLib:
     def masses(self, p, states: np.ndarray, n: int, ld: int, traj_len: int = 1) -> np.ndarray:
         """``kinematics``' arguments; returns (8, n): V_TT, V_TN, V_NN, ricci, eps_H, omega, M_eff2, mu_s2.  The masses object must be
         in place (``CompilationArtifact.ensure_masses``)."""
-        p = _f64(p, "p")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        p, P = _rows(p)
         out = np.empty((8, n))
         _check(self._lib.inflx_masses(self._h, _ptr(p), P, self.n_parameters, _ptr(states), int(n), int(ld), int(traj_len), _ptr(out)))
         return out
@@ -695,9 +672,7 @@ class InflatoxDevLib:
     def masses_device(self, p, d_states_ptr: int, d_states_bytes: int, n: int, ld: int, traj_len: int, d_out_ptr: int, d_out_bytes: int, stream: int = 0) -> None:
         """``masses`` on device arrays (include/inflx_hip.h: inflx_masses_device), with ``kinematics_device``'s arguments: the planes
         (8, n) to ``d_out_ptr``."""
-        p = _f64(p, "p")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        p, P = _rows(p)
         _check(
             self._lib.inflx_masses_device(
                 self._h, _ptr(p), P, self.n_parameters, C.c_void_p(d_states_ptr), int(d_states_bytes), int(n), int(ld), int(traj_len), C.c_void_p(d_out_ptr),
@@ -713,17 +688,11 @@ class InflatoxDevLib:
         n_stored (uint32)).  ``flags``: ``EOM_STOP_AT_END`` or 0.  The transfer object must be in place
         (``CompilationArtifact.ensure_transfer``)."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         samples = _f64(samples, "samples")
-        if samples.ndim != 1:
-            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        _one_dimensional(samples)
         B, S = init.shape[0], samples.size
-        if dq_dn is not None:
-            dq_dn = _f64(dq_dn, "dq_dn")
-            if dq_dn.shape != (B,):
-                raise InflatoxShapeError(f"dq_dn must have shape ({B},) (got {dq_dn.shape})")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        dq_dn = _optional_lanes(dq_dn, "dq_dn", B)
         out = np.empty((S, 10, B))
         ends = np.empty((B, 2))
         efolds = np.empty(B)
@@ -732,8 +701,8 @@ class InflatoxDevLib:
         _check(
             self._lib.inflx_transfer_functions(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, None if dq_dn is None else _ptr(dq_dn), _ptr(samples), S, int(max_steps), int(method),
-                float(max_err), float(dt), int(flags), _ptr(out), _ptr(ends), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
-                n_stored.ctypes.data_as(C.POINTER(C.c_uint32)),
+                float(max_err), float(dt), int(flags), _ptr(out), _ptr(ends), _ptr(efolds), _typed(status, C.c_int8),
+                _typed(n_stored, C.c_uint32),
             )
         )  # fmt: skip
         return out, ends, efolds, status, n_stored
@@ -747,21 +716,19 @@ class InflatoxDevLib:
         With ``MODES_TENSOR`` in ``flags`` the lanes carry one tensor mode instead (csrc/inflx_tensor.h): out is (8, n) -- P_T, Re ht,
         Im ht, Re pt, Im pt, N, t, epsilon_H -- and the tensor object must be in place (``CompilationArtifact.ensure_tensor``)."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         kappa = _f64(kappa, "kappa")
         n_target = _f64(n_target, "n_target")
         n = init.shape[0]
         if kappa.shape != (n,) or n_target.shape != (n,):
             raise InflatoxShapeError(f"kappa and n_target must have shape ({n},) (got {kappa.shape} and {n_target.shape})")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
         out = np.empty((8 if int(flags) & MODES_TENSOR else 22, n))
         efolds = np.empty(n)
         status = np.empty(n, dtype=np.int8)
         _check(
             self._lib.inflx_mode_spectra(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), n, _ptr(kappa), _ptr(n_target), int(max_steps), int(method), float(max_err), float(dt),
-                int(flags), _ptr(out), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+                int(flags), _ptr(out), _ptr(efolds), _typed(status, C.c_int8),
             )
         )  # fmt: skip
         return out, efolds, status
@@ -774,7 +741,7 @@ class InflatoxDevLib:
         local N, the local t and epsilon_H, lane fastest, NaN for a sample the lane did not pass.  ``flags``: ``EOM_STOP_AT_END`` or 0.
         The evolution object must be in place (``CompilationArtifact.ensure_evolution``)."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         kappa = _f64(kappa, "kappa")
         n_target = _f64(n_target, "n_target")
         shift = _f64(shift, "shift")
@@ -782,11 +749,8 @@ class InflatoxDevLib:
         n = init.shape[0]
         if kappa.shape != (n,) or n_target.shape != (n,) or shift.shape != (n,):
             raise InflatoxShapeError(f"kappa, n_target and shift must have shape ({n},) (got {kappa.shape}, {n_target.shape} and {shift.shape})")
-        if samples.ndim != 1:
-            raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+        _one_dimensional(samples)
         S = samples.shape[0]
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
         out = np.empty((22, n))
         sampled = np.empty((S, EV_SAMPLE_PLANES, n))
         efolds = np.empty(n)
@@ -794,7 +758,7 @@ class InflatoxDevLib:
         _check(
             self._lib.inflx_mode_evolution(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(init), n, _ptr(kappa), _ptr(n_target), _ptr(shift), _ptr(samples), S, int(max_steps), int(method),
-                float(max_err), float(dt), int(flags), _ptr(out), _ptr(sampled), _ptr(efolds), status.ctypes.data_as(C.POINTER(C.c_int8)),
+                float(max_err), float(dt), int(flags), _ptr(out), _ptr(sampled), _ptr(efolds), _typed(status, C.c_int8),
             )
         )  # fmt: skip
         return out, sampled, efolds, status
@@ -806,18 +770,13 @@ class InflatoxDevLib:
         N, N_,I, N_,IJ, N_;IJ, |grad N|^2, f_NL, P_zeta, status, stencil fastest; surface (2, B): H_c, N_c; status (int32)).  The
         delta-N object must be in place (``CompilationArtifact.ensure_deltan``)."""
         centre = _f64(centre, "centre")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         B = centre.shape[0]
         if vel is not None:
             vel = _f64(vel, "vel")
             if vel.shape != (B, 9, 2):
                 raise InflatoxShapeError(f"vel must have shape ({B}, 9, 2) (got {vel.shape})")
-        if h_end is not None:
-            h_end = _f64(h_end, "h_end")
-            if h_end.shape != (B,):
-                raise InflatoxShapeError(f"h_end must have shape ({B},) (got {h_end.shape})")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        h_end = _optional_lanes(h_end, "h_end", B)
         out = np.empty((DN_OUT_PLANES, B))
         surface = np.empty((2, B))
         status = np.empty(B, dtype=np.int32)
@@ -825,7 +784,7 @@ class InflatoxDevLib:
             self._lib.inflx_delta_n(
                 self._h, _ptr(p), P, self.n_parameters, _ptr(centre), B, None if vel is None else _ptr(vel), int(rule), float(h0), float(h1),
                 None if h_end is None else _ptr(h_end), int(max_steps), int(method), float(max_err), float(dt), _ptr(out), _ptr(surface),
-                status.ctypes.data_as(C.POINTER(C.c_int32)),
+                _typed(status, C.c_int32),
             )
         )  # fmt: skip
         return out, surface, status
@@ -838,19 +797,14 @@ class InflatoxDevLib:
         ended inflation and the lanes per status 0..5, point fastest; samples (7, B * R): N, phi^0, phi^1, chi^0, chi^1, H, status,
         lane b * R + r fastest -- or None).  The stochastic object must be in place (``CompilationArtifact.ensure_stochastic``)."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         B = init.shape[0]
-        if streams is not None:
-            streams = np.ascontiguousarray(streams, dtype=np.uint32)
-            if streams.shape != (B,):
-                raise InflatoxShapeError(f"streams must have shape ({B},) (got {streams.shape})")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        streams = _streams(streams, B)
         moments = np.empty((ST_OUT_PLANES, B))
         samples = np.empty((ST_SAMPLE_PLANES, B * int(R))) if want_samples else None
         _check(
             self._lib.inflx_stochastic_efolds(
-                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(R), None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint32)),
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(R), None if streams is None else _typed(streams, C.c_uint32),
                 int(seed), float(noise_scale), float(dn_max), float(n_stop), int(max_steps), int(method), float(max_err), float(dt), _ptr(moments),
                 None if samples is None else _ptr(samples),
             )
@@ -866,26 +820,20 @@ class InflatoxDevLib:
         realisations that ended inflation; counts (B, 6) uint32: the realisations per status 0..5).  The distribution object must be
         in place (``CompilationArtifact.ensure_distribution``)."""
         init = _f64(init, "init")
-        p = _f64(p, "p")
+        p, P = _rows(p)
         ranges = _f64(ranges, "ranges")
         B = init.shape[0]
         if ranges.ndim != 2 or ranges.shape[1] != 2 or ranges.shape[0] not in (1, B):
             raise InflatoxShapeError(f"ranges must have shape (1, 2) or ({B}, 2) (got {ranges.shape})")
-        if streams is not None:
-            streams = np.ascontiguousarray(streams, dtype=np.uint32)
-            if streams.shape != (B,):
-                raise InflatoxShapeError(f"streams must have shape ({B},) (got {streams.shape})")
-        P = 1 if p.ndim <= 1 else p.shape[0]
-        p = p.reshape(-1)
+        streams = _streams(streams, B)
         # (a number of bins the library refuses is refused before it writes: the rows need not hold that many)
         hist = np.zeros((B, min(max(int(bins), 0), PD_MAX_BINS) + 2), dtype=np.uint32)
         counts = np.zeros((B, 6), dtype=np.uint32)
-        u32 = C.POINTER(C.c_uint32)
         _check(
             self._lib.inflx_stochastic_distribution(
-                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(R), None if streams is None else streams.ctypes.data_as(u32), int(seed), int(first),
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), B, int(R), None if streams is None else _typed(streams, C.c_uint32), int(seed), int(first),
                 int(lanes_per_point), float(noise_scale), float(dn_max), int(max_steps), int(method), float(max_err), float(dt), int(bins), _ptr(ranges),
-                ranges.shape[0], hist.ctypes.data_as(u32), counts.ctypes.data_as(u32),
+                ranges.shape[0], _typed(hist, C.c_uint32), _typed(counts, C.c_uint32),
             )
         )  # fmt: skip
         return hist, counts
@@ -995,6 +943,45 @@ class InflatoxDevLib:
 
     def synchronize(self):
         _check(self._lib.inflx_synchronize(self._h))
+
+
+# ---- what the background wrappers of InflatoxDevLib share ---------------------------------------------------------------------------
+def _rows(p):
+    """Parameter rows, (n_par,) or (P, n_par), as the library takes them: (the values as one flat float64 array, P)."""
+    p = _f64(p, "p")
+    return p.reshape(-1), 1 if p.ndim <= 1 else p.shape[0]
+
+
+def _typed(a: np.ndarray, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def _one_dimensional(samples: np.ndarray) -> None:
+    if samples.ndim != 1:
+        raise InflatoxShapeError(f"samples must be one-dimensional (got shape {samples.shape})")
+
+
+def _lanes(a: np.ndarray, name: str, n: int) -> None:
+    if a.shape != (n,):
+        raise InflatoxShapeError(f"{name} must have shape ({n},) (got {a.shape})")
+
+
+def _optional_lanes(a, name: str, n: int):
+    """None, or ``a`` as an (n,) float64 array."""
+    if a is None:
+        return None
+    a = _f64(a, name)
+    _lanes(a, name, n)
+    return a
+
+
+def _streams(streams, n: int):
+    """None, or the stream ids of n points as an (n,) uint32 array."""
+    if streams is None:
+        return None
+    streams = np.ascontiguousarray(streams, dtype=np.uint32)
+    _lanes(streams, "streams", n)
+    return streams
 
 
 def host_threads(devices_at_work: int = 1) -> dict:

@@ -54,6 +54,7 @@ built into ``<artefact>.background`` on first use (``CompilationArtifact.ensure_
 
 from __future__ import annotations
 
+import contextlib
 import math
 import operator
 from typing import NamedTuple
@@ -186,13 +187,125 @@ def _pars(artifact, pars, B):
     return p
 
 
-def _check_batch(artifact, pars, steps, fields_init, derivatives_init, max_err, solver, dt, substeps):
-    """The argument checks of ``solve_eom_batch`` and ``solve_eom_batch_device``: (steps, substeps, max_err, dt, p, init (B, 4))."""
-    steps, substeps, max_err, dt = _check_common(artifact, steps, max_err, solver, dt, substeps)
+def _check_fields(fields_init, derivatives_init):
     x = np.ascontiguousarray(fields_init, dtype=np.float64)
     v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
     if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
         raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    return x, v
+
+
+def _check_samples(samples, name, noun, negative=False):
+    """A list of points shared by all trajectories, the argument ``name`` holding ``noun``: (S,) float64 with 1 <= S < 2^32, finite,
+    strictly increasing and, unless ``negative``, >= 0."""
+    try:
+        pts = np.ascontiguousarray(samples, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be convertible to a float64 array") from None
+    if pts.ndim != 1:
+        raise InflatoxShapeError(f"{name} must be one-dimensional (got shape {pts.shape})")
+    if pts.size < 1 or pts.size >= 2**32:
+        raise ValueError(f"the number of {noun} must be in [1, 2^32) (got {pts.size})")
+    if negative:
+        if not np.isfinite(pts).all():
+            raise ValueError(f"{name} must be finite")
+    elif not (np.isfinite(pts).all() and (pts >= 0.0).all()):
+        raise ValueError(f"{name} must be finite and >= 0")
+    if not (np.diff(pts) > 0.0).all():
+        raise ValueError(f"{name} must be strictly increasing")
+    return pts
+
+
+def _check_n_star(N_star):
+    try:
+        N_star = float(N_star)
+    except (TypeError, ValueError):
+        raise ValueError("N_star must be a number") from None
+    if not (math.isfinite(N_star) and N_star >= 0.0):
+        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    return N_star
+
+
+def _check_grid(start_stop, N0, N1, derivatives_init):
+    """The grid of a map and the velocities its trajectories start with: (start_stop as an array of four, N0, N1, d (2,))."""
+    ss = np.asarray(start_stop, dtype=np.float64)
+    if ss.size != 4:
+        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
+    N0, N1 = operator.index(N0), operator.index(N1)
+    if N0 < 1 or N1 < 1:
+        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
+    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
+    if d.size != 2:
+        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
+    return ss, N0, N1, d
+
+
+def _parameter_row(artifact, pars, who):
+    """The one parameter row of a map; ``who``: the map and its verb, for the message."""
+    p = _pars(artifact, pars, 1)
+    if p.ndim != 1:
+        raise InflatoxShapeError(f"{who} one parameter row")
+    return p
+
+
+def _grid_init(start_stop, N0, N1, d):
+    """The initial conditions (N0 N1, 4) of a map's trajectories, point i N1 + j at (x0[i], x1[j]) of ``grid_points`` with the
+    velocities ``d``."""
+    x0, x1 = grid_points(start_stop, N0, N1)
+    init = np.empty((N0 * N1, 4))
+    init[:, 0] = np.repeat(x0, N1)
+    init[:, 1] = np.tile(x1, N0)
+    init[:, 2:] = d
+    return init
+
+
+def _second_stage(state, status, status_dtype, planes, feature, run=None):
+    """The second stage of a two-stage map.  ``state`` (..., 5) and ``status`` (...) are the first stage's; ``run`` are the flat
+    indices of the lanes that go on (None: those whose status is ``TARGET``).  ``feature(x, v, run)`` runs on their fields and
+    velocities and returns one array per plane, (n, *planes[i]), and the lanes' status.  Returns (the planes, (..., *planes[i]) each
+    and NaN on every other lane; ``status`` as ``status_dtype``, overwritten on the lanes that ran)."""
+    lead = status.shape
+    flat = state.reshape(-1, 5)
+    status = status.astype(status_dtype).reshape(-1)
+    out = [np.full((status.size, *shape), np.nan) for shape in planes]
+    if run is None:
+        run = np.flatnonzero(status == TARGET)
+    if run.size:
+        values, status[run] = feature(flat[run, :2], flat[run, 2:4], run)
+        for plane, got in zip(out, values):
+            plane[run] = got
+    return [plane.reshape(*lead, *shape) for plane, shape in zip(out, planes)], status.reshape(lead)
+
+
+def _companion_dylib(artifact, *what):
+    """The artefact's handle, with the companion objects ``what`` built first (``CompilationArtifact.ensure_<what>``)."""
+    for name in what:
+        getattr(artifact, "ensure_" + name)()
+    return _dylib(artifact, background=False)
+
+
+@contextlib.contextmanager
+def _side_stream(artifact, device, *tensors):
+    """The artefact's own torch stream, as an integer, for a native call on ``tensors``: ordered after what torch's current stream of
+    ``device`` has enqueued (the tensors were written or allocated there); afterwards the current stream is ordered after the call and
+    the tensors are recorded on the side stream."""
+    import torch
+
+    if getattr(artifact, "_background_torch_stream", None) is None:
+        artifact._background_torch_stream = torch.cuda.Stream(device=device)
+    side = artifact._background_torch_stream
+    consumer = torch.cuda.current_stream(device)
+    side.wait_stream(consumer)
+    yield side.cuda_stream
+    consumer.wait_stream(side)
+    for tensor in tensors:
+        tensor.record_stream(side)
+
+
+def _check_batch(artifact, pars, steps, fields_init, derivatives_init, max_err, solver, dt, substeps):
+    """The argument checks of ``solve_eom_batch`` and ``solve_eom_batch_device``: (steps, substeps, max_err, dt, p, init (B, 4))."""
+    steps, substeps, max_err, dt = _check_common(artifact, steps, max_err, solver, dt, substeps)
+    x, v = _check_fields(fields_init, derivatives_init)
     p = _pars(artifact, pars, x.shape[0])
     return steps, substeps, max_err, dt, p, np.concatenate([x, v], axis=1)
 
@@ -230,19 +343,12 @@ def solve_eom_batch_device(artifact: CompilationArtifact, pars, steps: int, fiel
     lib = _dylib(artifact)
     B = init.shape[0]
     device = torch.device("cuda", lib.device)
-    if getattr(artifact, "_background_torch_stream", None) is None:
-        artifact._background_torch_stream = torch.cuda.Stream(device=device)
-    side = artifact._background_torch_stream
     states = torch.empty((B, steps, 6), dtype=torch.float64, device=device)
     t = torch.empty((B, steps), dtype=torch.float64, device=device)
     if B:
-        consumer = torch.cuda.current_stream(device)
-        side.wait_stream(consumer)  # the tensors were allocated on the consumer's stream
-        n_end, status, last_row = lib.solve_eom_device(p, init, steps, substeps, _METHODS[solver], max_err, dt or 0.0, flags, states.data_ptr(),
-                                                       states.numel() * 8, t.data_ptr(), t.numel() * 8, stream=side.cuda_stream)  # fmt: skip
-        consumer.wait_stream(side)
-        states.record_stream(side)
-        t.record_stream(side)
+        with _side_stream(artifact, device, states, t) as stream:
+            n_end, status, last_row = lib.solve_eom_device(p, init, steps, substeps, _METHODS[solver], max_err, dt or 0.0, flags, states.data_ptr(),
+                                                           states.numel() * 8, t.data_ptr(), t.numel() * 8, stream=stream)  # fmt: skip
     else:
         n_end, status, last_row = np.empty(0), np.empty(0, dtype=np.int8), np.empty(0, dtype=np.int64)
     return EoMSolution(states[:, :, :5], t, states[:, :, 5], status, last_row, n_end)
@@ -288,23 +394,9 @@ def efolds_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int
     ``solve_eom_batch(..., stop_at_end=True)`` with a small fixed ``dt``.  A point already past the end of inflation (epsilon_H >= 1
     at the start) has N_end = 0."""
     _, _, max_err, _ = _check_common(artifact, max_steps, max_err, solver, None)
-    ss = np.asarray(start_stop, dtype=np.float64)
-    if ss.size != 4:
-        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
-    N0, N1 = operator.index(N0), operator.index(N1)
-    if N0 < 1 or N1 < 1:
-        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
-    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
-    if d.size != 2:
-        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
-    p = _pars(artifact, pars, 1)
-    if p.ndim != 1:
-        raise InflatoxShapeError("efolds_map takes one parameter row")
-    x0, x1 = grid_points(ss, N0, N1)
-    init = np.empty((N0 * N1, 4))
-    init[:, 0] = np.repeat(x0, N1)
-    init[:, 1] = np.tile(x1, N0)
-    init[:, 2:] = d
+    ss, N0, N1, d = _check_grid(start_stop, N0, N1, derivatives_init)
+    p = _parameter_row(artifact, pars, "efolds_map takes")
+    init = _grid_init(ss, N0, N1, d)
     flags = _native.EOM_STOP_AT_END | _native.EOM_FINAL_ONLY
     _, _, n_end, status, _ = _dylib(artifact).solve_eom(p, init, int(max_steps) + 1, 1, _METHODS[solver], max_err, 0.0, flags)
     n_end = np.where(status == ENDED, n_end, np.nan).reshape(N0, N1)
@@ -324,10 +416,7 @@ def state_at_efolds(artifact: CompilationArtifact, pars, fields_init, derivative
     ``max_steps`` accepted steps without reaching its target is ``COMPLETE``.  Bad arguments raise before anything runs on the
     device."""
     max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    x, v = _check_fields(fields_init, derivatives_init)
     B = x.shape[0]
     target = np.asarray(N_target, dtype=np.float64)
     if target.ndim == 0:
@@ -361,22 +450,8 @@ def solve_eom_sampled(artifact: CompilationArtifact, pars, samples, fields_init,
     max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
     if at not in ("N", "t"):
         raise ValueError(f"unknown sampling variable {at!r}: choose 'N' or 't'")
-    try:
-        pts = np.ascontiguousarray(samples, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("samples must be convertible to a float64 array") from None
-    if pts.ndim != 1:
-        raise InflatoxShapeError(f"samples must be one-dimensional (got shape {pts.shape})")
-    if pts.size < 1 or pts.size >= 2**32:
-        raise ValueError(f"the number of samples must be in [1, 2^32) (got {pts.size})")
-    if not (np.isfinite(pts).all() and (pts >= 0.0).all()):
-        raise ValueError("samples must be finite and >= 0")
-    if not (np.diff(pts) > 0.0).all():
-        raise ValueError("samples must be strictly increasing")
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    pts = _check_samples(samples, "samples", "samples")
+    x, v = _check_fields(fields_init, derivatives_init)
     p = _pars(artifact, pars, x.shape[0])
     init = np.concatenate([x, v], axis=1)
     flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.EOM_SAMPLE_T if at == "t" else 0)
@@ -395,9 +470,7 @@ def horizon_exit_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N
     ``return_status=True`` adds the (N0, N1) int8 status map: ``TARGET`` where the state was found, ``ENDED_SHORT`` where
     inflation ended after fewer than ``N_star`` e-folds, and the first pass's status (``COMPLETE``: never ended, or a failure)
     otherwise.  The state carries the error of N_end (see ``efolds_map``) times |dphi/dN|."""
-    N_star = float(N_star)
-    if not (math.isfinite(N_star) and N_star >= 0.0):
-        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    N_star = _check_n_star(N_star)
     n_end, status = efolds_map(artifact, pars, start_stop, N0, N1, derivatives_init, max_steps, max_err, solver, return_status=True)
     N0, N1 = n_end.shape
     status = status.copy().reshape(-1)
@@ -408,10 +481,8 @@ def horizon_exit_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N
     with np.errstate(invalid="ignore"):
         run = np.flatnonzero(ended & (flat_end >= N_star))
     if run.size:
-        x0, x1 = grid_points(start_stop, N0, N1)
-        x = np.stack([np.repeat(x0, N1), np.tile(x1, N0)], axis=1)[run]
-        v = np.broadcast_to(np.asarray(derivatives_init, dtype=np.float64).reshape(2), x.shape)
-        got = state_at_efolds(artifact, pars, x, v, flat_end[run] - N_star, max_steps, max_err, solver)
+        init = _grid_init(start_stop, N0, N1, np.asarray(derivatives_init, dtype=np.float64).reshape(2))[run]
+        got = state_at_efolds(artifact, pars, init[:, :2], init[:, 2:], flat_end[run] - N_star, max_steps, max_err, solver)
         state[run] = got.state
         status[run] = got.status
     state = state.reshape(N0, N1, 5)
@@ -513,27 +584,17 @@ def _state_pass(what: str, result, artifact: CompilationArtifact, pars, states):
             ld = _state_stride(shape, tuple(y.stride()))
             if ld is None:
                 y, ld = y.contiguous(), 5
-            lib = _dylib(artifact, background=False)
-            getattr(artifact, "ensure_" + what)()
-            if getattr(artifact, "_background_torch_stream", None) is None:
-                artifact._background_torch_stream = torch.cuda.Stream(device=y.device)
-            side = artifact._background_torch_stream
-            consumer = torch.cuda.current_stream(y.device)
-            side.wait_stream(consumer)  # the states were written, and `out` allocated, on the consumer's stream
+            lib = _companion_dylib(artifact, what)
             held = y.untyped_storage().nbytes() - y.storage_offset() * 8  # what the tensor's storage holds from its first element on
-            getattr(lib, what + "_device")(p, y.data_ptr(), held, n, ld, traj_len, out.data_ptr(), out.numel() * 8, stream=side.cuda_stream)
-            consumer.wait_stream(side)
-            y.record_stream(side)
-            out.record_stream(side)
+            with _side_stream(artifact, y.device, y, out) as stream:
+                getattr(lib, what + "_device")(p, y.data_ptr(), held, n, ld, traj_len, out.data_ptr(), out.numel() * 8, stream=stream)
         return result(*out.reshape((planes, *lead)))
     if n == 0:
         return result(*np.empty((planes, *lead)))
     ld = _state_stride(shape, tuple(st // 8 if st % 8 == 0 else 0 for st in y.strides))
     if ld is None or ld > _HOST_MAX_LD:
         y, ld = np.ascontiguousarray(y), 5
-    lib = _dylib(artifact, background=False)
-    getattr(artifact, "ensure_" + what)()
-    out = getattr(lib, what)(p, y, n, ld, traj_len)
+    out = getattr(_companion_dylib(artifact, what), what)(p, y, n, ld, traj_len)
     return result(*out.reshape((planes, *lead)))
 
 
@@ -666,29 +727,13 @@ def transfer_functions(artifact: CompilationArtifact, pars, samples, fields_init
     once with NaN everywhere.  The kernels are built into ``<artefact>.transfer`` on first use
     (``CompilationArtifact.ensure_transfer``).  Bad arguments raise before anything runs on the device."""
     max_steps, _, max_err, dt = _check_common(artifact, max_steps, max_err, solver, dt)
-    try:
-        pts = np.ascontiguousarray(samples, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("samples must be convertible to a float64 array") from None
-    if pts.ndim != 1:
-        raise InflatoxShapeError(f"samples must be one-dimensional (got shape {pts.shape})")
-    if pts.size < 1 or pts.size >= 2**32:
-        raise ValueError(f"the number of samples must be in [1, 2^32) (got {pts.size})")
-    if not (np.isfinite(pts).all() and (pts >= 0.0).all()):
-        raise ValueError("samples must be finite and >= 0")
-    if not (np.diff(pts) > 0.0).all():
-        raise ValueError("samples must be strictly increasing")
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    pts = _check_samples(samples, "samples", "samples")
+    x, v = _check_fields(fields_init, derivatives_init)
     p = _pars(artifact, pars, x.shape[0])
     dq = _check_dq_dN(dq_dN, x.shape[0])
     init = np.concatenate([x, v], axis=1)
     flags = _native.EOM_STOP_AT_END if stop_at_end else 0
-    artifact.ensure_transfer()
-    lib = _dylib(artifact, background=False)
-    out, ends, n_end, status, n_stored = lib.transfer_functions(p, init, dq, pts, max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
+    out, ends, n_end, status, n_stored = _companion_dylib(artifact, "transfer").transfer_functions(p, init, dq, pts, max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
     ended = status == ENDED
     return TransferSolution(out[:, 8].T, out[:, 9].T, out[:, 6].T, out[:, 5].T, out[:, 7].T, out[:, :5].transpose(2, 0, 1), n_stored,
                             np.where(ended, n_end, np.nan), np.where(ended, ends[:, 0], np.nan), np.where(ended, ends[:, 1], np.nan), status)  # fmt: skip
@@ -718,16 +763,12 @@ def transfer_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: i
         if not per_point:
             dq_dN = np.full(max(n_grid, 0), dq_dN[0])
     state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
-    N0, N1 = n_end.shape
-    flat = state.reshape(-1, 5)
-    status = status.copy().reshape(-1)
-    t_rs, t_ss = np.full(N0 * N1, np.nan), np.full(N0 * N1, np.nan)
-    run = np.flatnonzero(status == TARGET)
-    if run.size:
-        tf = transfer_functions(artifact, pars, [0.0], flat[run, :2], flat[run, 2:4], max_steps, max_err, solver, dq_dN=None if dq_dN is None else dq_dN[run])
-        t_rs[run], t_ss[run] = tf.T_RS_end, tf.T_SS_end
-        status[run] = tf.status
-    t_rs, t_ss, status = t_rs.reshape(N0, N1), t_ss.reshape(N0, N1), status.reshape(N0, N1)
+
+    def to_the_end(x, v, run):
+        tf = transfer_functions(artifact, pars, [0.0], x, v, max_steps, max_err, solver, dq_dN=None if dq_dN is None else dq_dN[run])
+        return (tf.T_RS_end, tf.T_SS_end), tf.status
+
+    (t_rs, t_ss), status = _second_stage(state, status, np.int8, [(), ()], to_the_end)
     return ((t_rs, t_ss), state, n_end, status) if return_status else ((t_rs, t_ss), state, n_end)
 
 
@@ -788,10 +829,7 @@ def _check_spectra(artifact, pars, N_exit, fields_init, derivatives_init, N_eval
             raise ValueError("N_eval must be None or a number") from None
         if not (math.isfinite(N_eval) and N_eval > n_exit.max()):
             raise ValueError(f"N_eval must be finite and > max(N_exit) = {n_exit.max()} (got {N_eval})")
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    x, v = _check_fields(fields_init, derivatives_init)
     B, K = x.shape[0], n_exit.size
     p = _pars(artifact, pars, B)
     return p, n_exit, x, v, N_eval, N_sub, max_steps, max_err, solver, dt, stop_at_end
@@ -806,11 +844,7 @@ def _mode_lanes(artifact, tensor, p, n_exit, x, v, N_eval, N_sub, max_steps, max
     out = np.full((8 if tensor else 22, B * K), np.nan)
     n_end = np.full(B * K, np.nan)
     if run.size:
-        if tensor:
-            artifact.ensure_tensor()
-        else:
-            artifact.ensure_modes()
-        lib = _dylib(artifact, background=False)
+        lib = _companion_dylib(artifact, "tensor" if tensor else "modes")
         flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.MODES_TENSOR if tensor else 0)
         got, ends, st = lib.mode_spectra(lane_p, init, kappa, target, max_steps, _METHODS[solver], max_err, dt or 0.0, flags)
         _mode_stage2_result(out, n_end, status, run, N_eval, got, ends, st)
@@ -905,23 +939,14 @@ def spectrum_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: i
     ``return_status=True`` adds the (N0, N1) status map: ``horizon_exit_map``'s, with the second stage's status (``ENDED`` where the
     spectra are valid) in place of ``TARGET``."""
     N_sub = _check_n_sub(N_sub)
-    try:
-        N_star = float(N_star)
-    except (TypeError, ValueError):
-        raise ValueError("N_star must be a number") from None
-    if not (math.isfinite(N_star) and N_star >= 0.0):
-        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    N_star = _check_n_star(N_star)
     state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star + N_sub, derivatives_init, max_steps, max_err, solver, return_status=True)
-    N0, N1 = n_end.shape
-    flat = state.reshape(-1, 5)
-    status = status.copy().reshape(-1)
-    spectra = np.full((3, N0 * N1), np.nan)
-    run = np.flatnonzero(status == TARGET)
-    if run.size:
-        ps = power_spectra(artifact, pars, [N_sub], flat[run, :2], flat[run, 2:4], N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver)
-        spectra[:, run] = ps.P_R[:, 0], ps.P_S[:, 0], ps.C_RS[:, 0]
-        status[run] = ps.status[:, 0]
-    spectra, status = spectra.reshape(3, N0, N1), status.reshape(N0, N1)
+
+    def to_the_end(x, v, run):
+        ps = power_spectra(artifact, pars, [N_sub], x, v, N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver)
+        return (ps.P_R[:, 0], ps.P_S[:, 0], ps.C_RS[:, 0]), ps.status[:, 0]
+
+    spectra, status = _second_stage(state, status, np.int8, [()] * 3, to_the_end)
     return (tuple(spectra), state, n_end, status) if return_status else (tuple(spectra), state, n_end)
 
 
@@ -1005,8 +1030,7 @@ def spectra_evolution(artifact: CompilationArtifact, pars, N_exit, samples, fiel
     n_end = np.full(B * K, np.nan)
     sampled = np.full((S, _native.EV_SAMPLE_PLANES, B * K), np.nan)
     if run.size:
-        artifact.ensure_evolution()
-        lib = _dylib(artifact, background=False)
+        lib = _companion_dylib(artifact, "evolution")
         got, sm, ends, st = lib.mode_evolution(lane_p, init, kappa, target, np.ascontiguousarray(np.tile(shift, B)[run]), samples, max_steps, _METHODS[solver],
                                                max_err, dt or 0.0, _native.EOM_STOP_AT_END if stop_at_end else 0)  # fmt: skip
         _mode_stage2_result(out, n_end, status, run, N_eval, got, ends, st)
@@ -1033,25 +1057,15 @@ def evolution_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: 
     ``horizon_exit_map``'s at ``N_star + N_sub``.  NaN where no such state was found and at a sample the second stage did not reach;
     ``return_status=True`` adds the (N0, N1) status map as ``spectrum_map`` does."""
     N_sub = _check_n_sub(N_sub)
-    try:
-        N_star = float(N_star)
-    except (TypeError, ValueError):
-        raise ValueError("N_star must be a number") from None
-    if not (math.isfinite(N_star) and N_star >= 0.0):
-        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    N_star = _check_n_star(N_star)
     samples, _ = _check_evolution_samples(samples, "exit", np.array([N_sub]), None, N_sub)
     state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star + N_sub, derivatives_init, max_steps, max_err, solver, return_status=True)
-    N0, N1 = n_end.shape
-    flat = state.reshape(-1, 5)
-    status = status.copy().reshape(-1)
-    spectra = np.full((3, N0 * N1, samples.size), np.nan)
-    run = np.flatnonzero(status == TARGET)
-    if run.size:
-        ev = spectra_evolution(artifact, pars, [N_sub], samples, flat[run, :2], flat[run, 2:4], since="exit", N_sub=N_sub, max_steps=max_steps, max_err=max_err,
-                               solver=solver)  # fmt: skip
-        spectra[:, run] = ev.P_R[:, 0], ev.P_S[:, 0], ev.C_RS[:, 0]
-        status[run] = ev.status[:, 0]
-    spectra, status = spectra.reshape(3, N0, N1, samples.size), status.reshape(N0, N1)
+
+    def to_the_end(x, v, run):
+        ev = spectra_evolution(artifact, pars, [N_sub], samples, x, v, since="exit", N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver)
+        return (ev.P_R[:, 0], ev.P_S[:, 0], ev.C_RS[:, 0]), ev.status[:, 0]
+
+    spectra, status = _second_stage(state, status, np.int8, [(samples.size,)] * 3, to_the_end)
     return (tuple(spectra), state, n_end, status) if return_status else (tuple(spectra), state, n_end)
 
 
@@ -1245,24 +1259,15 @@ def observables_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1
     ``observables``' status (``ENDED`` where the values are valid) in place of ``TARGET``."""
     N_sub = _check_n_sub(N_sub)
     dN = _check_dn(dN)
-    try:
-        N_star = float(N_star)
-    except (TypeError, ValueError):
-        raise ValueError("N_star must be a number") from None
-    if not (math.isfinite(N_star) and N_star >= 0.0):
-        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    N_star = _check_n_star(N_star)
     state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star + N_sub + dN, derivatives_init, max_steps, max_err, solver, return_status=True)
-    N0, N1 = n_end.shape
-    flat = state.reshape(-1, 5)
-    status = status.copy().reshape(-1)
-    values = np.full((len(Observables._fields) - 1, N0 * N1), np.nan)
-    run = np.flatnonzero(status == TARGET)
-    if run.size:
-        obs = observables(artifact, pars, [N_sub + dN], flat[run, :2], flat[run, 2:4], dN=dN, N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver)
-        values[:, run] = [member[:, 0] for member in obs[:-1]]
-        status[run] = obs.status[:, 0]
-    status = status.reshape(N0, N1)
-    obs = Observables(*values.reshape(-1, N0, N1), status)
+
+    def to_the_end(x, v, run):
+        obs = observables(artifact, pars, [N_sub + dN], x, v, dN=dN, N_sub=N_sub, max_steps=max_steps, max_err=max_err, solver=solver)
+        return [member[:, 0] for member in obs[:-1]], obs.status[:, 0]
+
+    values, status = _second_stage(state, status, np.int8, [()] * (len(Observables._fields) - 1), to_the_end)
+    obs = Observables(*values, status)
     return (obs, state, n_end, status) if return_status else (obs, state, n_end)
 
 
@@ -1380,8 +1385,7 @@ def delta_N(artifact: CompilationArtifact, pars, fields_init, derivatives_init=N
     ``<artefact>.deltan`` on first use (``CompilationArtifact.ensure_deltan``).  Returns a :class:`DeltaN`."""
     p, centre, vel, rule, h0, h1, h_end, max_steps, max_err, dt = _check_delta_n(artifact, pars, fields_init, derivatives_init, h, velocity, H_end, max_steps, max_err,
                                                                                  solver, dt)  # fmt: skip
-    artifact.ensure_deltan()
-    out, surface, status = _dylib(artifact, background=False).delta_n(p, centre, vel, rule, h0, h1, h_end, max_steps, _METHODS[solver], max_err, dt or 0.0)
+    out, surface, status = _companion_dylib(artifact, "deltan").delta_n(p, centre, vel, rule, h0, h1, h_end, max_steps, _METHODS[solver], max_err, dt or 0.0)
     return _delta_n_result(out, surface, status)
 
 
@@ -1395,26 +1399,16 @@ def fnl_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1: int, N
     exit state was found; ``dn.status`` and, with ``return_status=True``, a fourth member are the (N0, N1) int16 status map:
     ``horizon_exit_map``'s, with ``delta_N``'s status (``LOCATED`` where the values are valid) in place of ``TARGET``."""
     _check_delta_n_options(artifact, h, velocity, max_steps, max_err, solver, None)
-    try:
-        N_star = float(N_star)
-    except (TypeError, ValueError):
-        raise ValueError("N_star must be a number") from None
-    if not (math.isfinite(N_star) and N_star >= 0.0):
-        raise ValueError(f"N_star must be finite and >= 0 (got {N_star})")
+    N_star = _check_n_star(N_star)
     state, n_end, status = horizon_exit_map(artifact, pars, start_stop, N0, N1, N_star, derivatives_init, max_steps, max_err, solver, return_status=True)
-    N0, N1 = n_end.shape
-    flat = state.reshape(-1, 5)
-    status = status.astype(np.int16).reshape(-1)
     shapes = {"N_members": (3, 3), "N_I": (2,), "N_IJ": (2, 2), "N_cov": (2, 2)}
-    values = {name: np.full((N0 * N1, *shapes.get(name, ())), np.nan) for name in DeltaN._fields[:-1]}
-    run = np.flatnonzero(status == TARGET)
-    if run.size:
-        dn = delta_N(artifact, pars, flat[run, :2], flat[run, 2:4], h=h, velocity=velocity, max_steps=max_steps, max_err=max_err, solver=solver)
-        for name in values:
-            values[name][run] = getattr(dn, name)
-        status[run] = dn.status
-    status = status.reshape(N0, N1)
-    dn = DeltaN(*(values[name].reshape(N0, N1, *shapes.get(name, ())) for name in DeltaN._fields[:-1]), status)
+
+    def to_the_end(x, v, run):
+        dn = delta_N(artifact, pars, x, v, h=h, velocity=velocity, max_steps=max_steps, max_err=max_err, solver=solver)
+        return dn[:-1], dn.status
+
+    values, status = _second_stage(state, status, np.int16, [shapes.get(name, ()) for name in DeltaN._fields[:-1]], to_the_end)
+    dn = DeltaN(*values, status)
     return (dn, state, n_end, status) if return_status else (dn, state, n_end)
 
 
@@ -1495,8 +1489,7 @@ def _stochastic_result(moments, classical, samples, B, R) -> StochasticEfolds:
 
 
 def _stochastic_run(artifact, p, init, R, ids, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt, return_samples) -> StochasticEfolds:
-    artifact.ensure_stochastic()
-    lib = _dylib(artifact, background=False)
+    lib = _companion_dylib(artifact, "stochastic")
     method, B = _METHODS[solver], init.shape[0]
     moments, samples = lib.stochastic_efolds(p, init, R, ids, seed, noise_scale, dN_max, N_stop, max_steps, method, max_err, dt or 0.0, return_samples)
     # the classical trajectory: the same entry point with one realisation and no noise (moments: its N_end is the mean and the minimum)
@@ -1532,10 +1525,7 @@ def stochastic_efolds(artifact: CompilationArtifact, pars, fields_init, derivati
     :class:`StochasticEfolds`."""
     R, seed, noise_scale, dN_max, N_stop, max_steps, max_err, dt = _check_stochastic_options(artifact, realisations, seed, noise_scale, dN_max, N_stop, max_steps,
                                                                                              max_err, solver, dt)  # fmt: skip
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    x, v = _check_fields(fields_init, derivatives_init)
     B = x.shape[0]
     ids = _check_streams(streams, B)
     p = _pars(artifact, pars, B)
@@ -1550,23 +1540,9 @@ def stochastic_map(artifact: CompilationArtifact, pars, start_stop, N0: int, N1:
     (N0, N1, 6)), the stream of a point its index in the flattened grid.  Beside ``GeneralisedAL.flag_quantum_dif`` over the same grid it
     says what the diffusion does where that flag is set.  It never returns samples."""
     options = _check_stochastic_options(artifact, realisations, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt)
-    ss = np.asarray(start_stop, dtype=np.float64)
-    if ss.size != 4:
-        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
-    N0, N1 = operator.index(N0), operator.index(N1)
-    if N0 < 1 or N1 < 1:
-        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
-    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
-    if d.size != 2:
-        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
-    p = _pars(artifact, pars, 1)
-    if p.ndim != 1:
-        raise InflatoxShapeError("stochastic_map takes one parameter row")
-    x0, x1 = grid_points(ss, N0, N1)
-    init = np.empty((N0 * N1, 4))
-    init[:, 0] = np.repeat(x0, N1)
-    init[:, 1] = np.tile(x1, N0)
-    init[:, 2:] = d
+    ss, N0, N1, d = _check_grid(start_stop, N0, N1, derivatives_init)
+    p = _parameter_row(artifact, pars, "stochastic_map takes")
+    init = _grid_init(ss, N0, N1, d)
     R, seed, noise_scale, dN_max, N_stop, max_steps, max_err, dt = options
     flat = _stochastic_run(artifact, p, init, R, None, seed, noise_scale, dN_max, N_stop, max_steps, max_err, solver, dt, False)
     return StochasticEfolds(*(a.reshape(N0, N1, *a.shape[1:]) for a in flat[:9]))
@@ -1662,9 +1638,7 @@ def _check_n_range(N_range, B):
 
 def _distribution_run(artifact, p, init, ranges, ids, centre, options, solver) -> StochasticDistribution:
     R, bins, seed, first, L, noise_scale, dN_max, max_steps, max_err, dt = options
-    artifact.ensure_stochastic()
-    artifact.ensure_distribution()
-    lib = _dylib(artifact, background=False)
+    lib = _companion_dylib(artifact, "stochastic", "distribution")
     method, B = _METHODS[solver], init.shape[0]
     ids = np.arange(B, dtype=np.uint32) if ids is None else ids
     # the classical trajectory as _stochastic_run finds it: one realisation and no noise (moments: its N_end is the mean)
@@ -1717,10 +1691,7 @@ def stochastic_distribution(artifact: CompilationArtifact, pars, fields_init, de
     runs on the device."""
     options = _check_distribution_options(artifact, realisations, bins, centre, seed, first_realisation, lanes_per_point, noise_scale, dN_max, max_steps, max_err,
                                           solver, dt)  # fmt: skip
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
+    x, v = _check_fields(fields_init, derivatives_init)
     B = x.shape[0]
     ids = _check_streams(streams, B)
     p = _pars(artifact, pars, B)
@@ -1740,24 +1711,10 @@ def stochastic_distribution_map(artifact: CompilationArtifact, pars, start_stop,
     A grid point whose classical run does not end has zero counts and NaN edges."""
     options = _check_distribution_options(artifact, realisations, bins, centre, seed, first_realisation, lanes_per_point, noise_scale, dN_max, max_steps, max_err,
                                           solver, dt)  # fmt: skip
-    ss = np.asarray(start_stop, dtype=np.float64)
-    if ss.size != 4:
-        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
-    N0, N1 = operator.index(N0), operator.index(N1)
-    if N0 < 1 or N1 < 1:
-        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
-    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
-    if d.size != 2:
-        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
-    p = _pars(artifact, pars, 1)
-    if p.ndim != 1:
-        raise InflatoxShapeError("stochastic_distribution_map takes one parameter row")
+    ss, N0, N1, d = _check_grid(start_stop, N0, N1, derivatives_init)
+    p = _parameter_row(artifact, pars, "stochastic_distribution_map takes")
     ranges = _check_n_range(N_range, N0 * N1)
-    x0, x1 = grid_points(ss, N0, N1)
-    init = np.empty((N0 * N1, 4))
-    init[:, 0] = np.repeat(x0, N1)
-    init[:, 1] = np.tile(x1, N0)
-    init[:, 2:] = d
+    init = _grid_init(ss, N0, N1, d)
     flat = _distribution_run(artifact, p, init, ranges, None, centre, options, solver)
     return StochasticDistribution(*(a.reshape(N0, N1, *a.shape[1:]) for a in flat[:7]), *flat[7:])
 
@@ -1877,19 +1834,7 @@ class ExitPoints(NamedTuple):
 
 
 def _check_ln_k(ln_k):
-    try:
-        pts = np.ascontiguousarray(ln_k, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("ln_k must be convertible to a float64 array") from None
-    if pts.ndim != 1:
-        raise InflatoxShapeError(f"ln_k must be one-dimensional (got shape {pts.shape})")
-    if pts.size < 1 or pts.size >= 2**32:
-        raise ValueError(f"the number of wavenumbers must be in [1, 2^32) (got {pts.size})")
-    if not np.isfinite(pts).all():
-        raise ValueError("ln_k must be finite")
-    if not (np.diff(pts) > 0.0).all():
-        raise ValueError("ln_k must be strictly increasing")
-    return pts
+    return _check_samples(ln_k, "ln_k", "wavenumbers", negative=True)
 
 
 def _check_offset(offset, B):
@@ -1908,17 +1853,8 @@ def _check_offset(offset, B):
     return np.ascontiguousarray(off)
 
 
-def _check_fields(fields_init, derivatives_init):
-    x = np.ascontiguousarray(fields_init, dtype=np.float64)
-    v = np.ascontiguousarray(derivatives_init, dtype=np.float64)
-    if x.ndim != 2 or x.shape[1] != 2 or v.shape != x.shape:
-        raise InflatoxShapeError(f"fields_init and derivatives_init must both have shape (B, 2) (got {x.shape} and {v.shape})")
-    return x, v
-
-
 def _crossing_dylib(artifact):
-    artifact.ensure_crossing()
-    return _dylib(artifact, background=False)
+    return _companion_dylib(artifact, "crossing")
 
 
 def horizon_crossings(artifact: CompilationArtifact, pars, ln_k, fields_init, derivatives_init, *, offset=None, max_steps: int = 100_000,
@@ -2030,11 +1966,7 @@ def _mode_lanes_at_k(artifact, tensor, p, pts, x, v, off, N_eval, N_sub, max_ste
         status[lanes] = np.where(found, TARGET, np.where(both.status[:n] != TARGET, both.status[:n], both.status[n:]))
         run = lanes[found]
         if run.size:
-            if tensor:
-                artifact.ensure_tensor()
-            else:
-                artifact.ensure_modes()
-            lib = _dylib(artifact, background=False)
+            lib = _companion_dylib(artifact, "tensor" if tensor else "modes")
             flags = (_native.EOM_STOP_AT_END if stop_at_end else 0) | (_native.MODES_TENSOR if tensor else 0)
             target = np.full(run.size, np.nan) if N_eval is None else N_eval - lane_start[run]
             kappa = h[found] * math.exp(N_sub)
@@ -2155,15 +2087,7 @@ def reheating_offset(k_mpc: float = 0.05, *, w_reh: float = 1.0 / 3.0, N_reh: fl
 def _check_pivot_grid(artifact, pars, start_stop, N0, N1, A, derivatives_init, max_steps, max_err, solver):
     """The argument checks of the pivot maps: (p, init (N0 N1, 4), A (N0 N1,), N0, N1, max_steps, max_err)."""
     max_steps, _, max_err, _ = _check_common(artifact, max_steps, max_err, solver, None)
-    ss = np.asarray(start_stop, dtype=np.float64)
-    if ss.size != 4:
-        raise InflatoxShapeError(f"start_stop must be [[x0_start, x0_stop], [x1_start, x1_stop]] (got shape {ss.shape})")
-    N0, N1 = operator.index(N0), operator.index(N1)
-    if N0 < 1 or N1 < 1:
-        raise ValueError(f"the grid needs at least one point per axis (got {N0} x {N1})")
-    d = np.asarray(derivatives_init, dtype=np.float64).reshape(-1)
-    if d.size != 2:
-        raise InflatoxShapeError(f"derivatives_init must hold two velocities (got {d.size})")
+    ss, N0, N1, d = _check_grid(start_stop, N0, N1, derivatives_init)
     try:
         a = np.asarray(A, dtype=np.float64)
     except (TypeError, ValueError):
@@ -2172,14 +2096,8 @@ def _check_pivot_grid(artifact, pars, start_stop, N0, N1, A, derivatives_init, m
         raise InflatoxShapeError(f"A must be a scalar or have shape ({N0}, {N1}) (got {a.shape})")
     if not np.isfinite(a).all():
         raise ValueError("A must be finite")
-    p = _pars(artifact, pars, 1)
-    if p.ndim != 1:
-        raise InflatoxShapeError("the pivot maps take one parameter row")
-    x0, x1 = grid_points(ss, N0, N1)
-    init = np.empty((N0 * N1, 4))
-    init[:, 0] = np.repeat(x0, N1)
-    init[:, 1] = np.tile(x1, N0)
-    init[:, 2:] = d
+    p = _parameter_row(artifact, pars, "the pivot maps take")
+    init = _grid_init(ss, N0, N1, d)
     return p, init, np.broadcast_to(a, (N0, N1)).reshape(-1), N0, N1, max_steps, max_err
 
 
@@ -2234,15 +2152,13 @@ def pivot_observables_map(artifact: CompilationArtifact, pars, start_stop, N0: i
     dlnk = _check_dlnk(dlnk)
     p, init, a, N0, N1, max_steps, max_err = _check_pivot_grid(artifact, pars, start_stop, N0, N1, A, derivatives_init, max_steps, max_err, solver)
     end, pivot, state, n_at, status = _pivot_crossing(artifact, p, init, a, -(dlnk + N_sub), max_steps, max_err, solver)
-    values = np.full((len(Observables._fields) - 1, N0 * N1), np.nan)
-    n_star = np.full(N0 * N1, np.nan)
-    run = np.flatnonzero(np.isfinite(n_at))
-    if run.size:
-        obs, n_exit = _observables_at_k(artifact, p, [0.0], state[run, :2], state[run, 2:4], dlnk, pivot[run] - n_at[run], None, N_sub, max_steps, max_err, solver,
-                                        None, True)  # fmt: skip
-        values[:, run] = [member[:, 0] for member in obs[:-1]]
-        status[run] = obs.status[:, 0]
-        n_star[run] = end.N_end[run] - (n_at[run] + n_exit[:, 0])
-    status = status.reshape(N0, N1)
-    out = (Observables(*values.reshape(-1, N0, N1), status), state.reshape(N0, N1, 5), n_star.reshape(N0, N1), end.N_end.reshape(N0, N1))
+
+    def to_the_end(x, v, run):
+        obs, n_exit = _observables_at_k(artifact, p, [0.0], x, v, dlnk, pivot[run] - n_at[run], None, N_sub, max_steps, max_err, solver, None, True)
+        return [member[:, 0] for member in obs[:-1]] + [end.N_end[run] - (n_at[run] + n_exit[:, 0])], obs.status[:, 0]
+
+    # every point whose restart state was located goes on, whatever its status
+    (*values, n_star), status = _second_stage(state.reshape(N0, N1, 5), status.reshape(N0, N1), np.int8, [()] * len(Observables._fields), to_the_end,
+                                              run=np.flatnonzero(np.isfinite(n_at)))  # fmt: skip
+    out = (Observables(*values, status), state.reshape(N0, N1, 5), n_star, end.N_end.reshape(N0, N1))
     return (*out, status) if return_status else out
