@@ -320,6 +320,12 @@ int inflx_synchronize(inflx_model* model);
  *                  sweeps, inflx_sweep_on_trajectory, inflx_sweep_device_stats, the *_multi forms, and inflx_synchronize for
  *                  the asynchronous device-resident sweeps) returns INFLX_ERR_GSL, with the reference handler's first line in
  *                  inflx_last_error(), AFTER the result has been written: the caller's array is complete, NaN at the points;
+ *                  a call that integrates trajectories (inflx_solve_eom and every entry point that follows its error policy) returns
+ *                  INFLX_ERR_GSL if and only if a bit is set AND a lane of the call stopped INFLX_EOM_NONFINITE -- the adaptive step
+ *                  control retries a trial step that left a function's domain with a shorter one, which sets the bit in a lane that
+ *                  goes on inside the domain -- and clears the bits otherwise.  (A retried trial in one lane together with an
+ *                  unrelated INFLX_EOM_NONFINITE in another still fails the call.)  inflx_kinematics and inflx_masses evaluate
+ *                  given states and fail on any bit;
  *   INFLX_SF_QUIET (default otherwise)        -- NaN at the points, INFLX_OK.
  * inflx_sf_status: OR of the bits (inflx_sf_bits) set since they were last cleared, after waiting for the handle's streams;
  * `clear` != 0 resets them.  Reported conditions: the argument domains GSL documents (nu >= 0; Y, K, y_l for x > 0; J_nu, I_nu, j_l

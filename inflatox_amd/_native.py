@@ -276,7 +276,9 @@ class InflatoxBasisError(Exception):
 class InflatoxSpecialFunctionError(ArithmeticError):
     """A special function of the model was called outside its domain somewhere in the call (``INFLX_ERR_GSL``).  The reference's
     GSL error handler prints the reason and panics at that point (src/err.rs:86-103): the call does not return there either.  Here
-    the result was complete when the error was raised -- NaN at the offending points -- and ``sf_errors="nan"`` returns it."""
+    the result was complete when the error was raised -- NaN at the offending points -- and ``sf_errors="nan"`` returns it.  From
+    ``inflatox_amd.background``: a call that integrates trajectories raises it when one of them stopped ``NONFINITE`` outside a
+    function's domain, and ``background.set_sf_errors(artifact, "nan")`` returns the result instead."""
 
 
 def _raise(rc: int):

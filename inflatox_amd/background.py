@@ -40,7 +40,8 @@ locates N, and ``inflation_end`` the state where epsilon_H = 1 on the same dense
 ``tensor_spectra_at_k`` and ``observables_at_k`` are ``power_spectra``, ``tensor_spectra`` and ``observables`` on a k-grid common to all
 trajectories; ``reheating_offset`` turns a physical wavenumber today and a reheating history into the offset of that grid, and
 ``pivot_exit_map`` and ``pivot_observables_map`` draw the exit state, N_star, n_s and r of such a pivot scale over a sweep grid, N_star
-following from every trajectory instead of being guessed.
+following from every trajectory instead of being guessed.  ``set_sf_errors`` chooses, for a model with special functions, between an
+error and NaN where a function's domain is left.
 
 The system (Planck units, cosmic time) is the reference's, y = (phi^0, phi^1, chi^0, chi^1, H) plus the e-fold count N::
 
@@ -72,7 +73,7 @@ __all__ = ["solve_eom", "solve_eom_batch", "solve_eom_batch_device", "efolds_map
            "stochastic_efolds", "stochastic_map", "StochasticEfolds", "stochastic_distribution", "stochastic_distribution_map", "StochasticDistribution",
            "distribution_pdf", "distribution_survival", "distribution_mean", "distribution_tail_rate", "horizon_crossings", "CrossingSolution", "inflation_end",
            "InflationEnd", "power_spectra_at_k", "tensor_spectra_at_k", "ExitPoints", "observables_at_k", "reheating_offset", "pivot_exit_map",
-           "pivot_observables_map", "OUTSIDE_AT_START"]  # fmt: skip
+           "pivot_observables_map", "OUTSIDE_AT_START", "set_sf_errors"]  # fmt: skip
 
 #: ``status`` codes of a trajectory (include/inflx_hip.h ``inflx_eom_status``)
 COMPLETE, ENDED, NONFINITE, REJECTED, UNDERFLOW, TARGET = 0, 1, 2, 3, 4, 5
@@ -147,6 +148,21 @@ def _dylib(artifact: CompilationArtifact, background: bool = True) -> _native.In
         lib = _native.InflatoxDevLib(artifact.shared_object_path)
         artifact._background_dylib = lib
     return lib
+
+
+def set_sf_errors(artifact: CompilationArtifact, mode: str) -> None:
+    """What the functions of this module do when a ``Compiler(link_gsl=True)`` model evaluated a Bessel or hypergeometric function
+    outside its domain -- the words and errors of ``GeneralisedAL(..., sf_errors=)``, applied to the artefact's background handle
+    (opened here when no call has opened it yet) and kept for every later call on the artefact.  ``"raise"`` (the default of such an
+    artefact): ``kinematics`` and ``masses`` raise :class:`InflatoxSpecialFunctionError` when a state lies outside the domain, and a
+    call that integrates trajectories raises it when one of them stopped ``NONFINITE`` there; a trial step that left the domain and was
+    retried with a shorter one raises nothing.  An ADAPTIVE trajectory that really reaches a domain's edge does not become ``NONFINITE``:
+    every trial that crosses the edge is retried shorter, the steps pile up in front of it and the trajectory stops ``UNDERFLOW`` --
+    it signals the exit through that status, not through the error; a fixed ``dt`` or a start outside the domain gives ``NONFINITE``.
+    ``"nan"``: every call returns its result, with NaN and ``NONFINITE`` where the domain
+    was left -- an ``efolds_map`` whose grid touches a domain edge holds NaN at those points."""
+    _native._sf_policy(mode)  # (a wrong word is refused before the handle is opened)
+    _dylib(artifact, background=False).set_sf_errors(mode)
 
 
 def _check_common(artifact, steps, max_err, solver, dt, substeps=1):

@@ -603,14 +603,22 @@ int sf_collect(inflx_model* m, bool clear, unsigned* bits) {
   return INFLX_OK;
 }
 
-int sf_error(const inflx_model* m, unsigned bits) {
+// `lanes`: the call integrates trajectories and reports a status per lane, which is where its message points
+int sf_error(const inflx_model* m, unsigned bits, bool lanes = false) {
   // (the first words are the reference handler's, src/err.rs:98 -- spelling included; GSL_EDOM = 1, GSL_ELOSS = 17)
   const bool dom = (bits & INFLX_SF_EDOM) != 0;
+  const char* code = dom ? "0X1" : "0X11";
+  const char* why = dom ? "outside its domain (input domain error)" : "where this implementation could not deliver 1e-13 and declined (loss of accuracy)";
+  if (lanes)
+    return fail(INFLX_ERR_GSL, "a GSL exception ocurred (ERRCODE %s): model \"%s\" called a special function %s on one or more trajectories of this call. "
+                "The trajectories whose status is INFLX_EOM_NONFINITE stopped there (a stencil or a point: those with such a lane) and the result is complete "
+                "otherwise; the reference's GSL error handler panics here instead of returning. "
+                "inflx_sf_policy(handle, INFLX_SF_QUIET) / background.set_sf_errors(artifact, \"nan\") returns the result with its NaNs.",
+                code, m->name.c_str(), why);
   return fail(INFLX_ERR_GSL, "a GSL exception ocurred (ERRCODE %s): model \"%s\" called a special function %s at one or more points of this call. "
               "Those points hold NaN and the result is complete otherwise; the reference's GSL error handler panics here instead of returning. "
               "inflx_sf_policy(handle, INFLX_SF_QUIET) / GeneralisedAL(..., sf_errors=\"nan\") returns the result with its NaNs.",
-              dom ? "0X1" : "0X11", m->name.c_str(),
-              dom ? "outside its domain (input domain error)" : "where this implementation could not deliver 1e-13 and declined (loss of accuracy)");
+              code, m->name.c_str(), why);
 }
 
 // what a host-result call returns after its result is complete
@@ -620,6 +628,18 @@ int sf_verdict(inflx_model* m) {
   const int rc = sf_collect(m, true, &bits);
   if (rc) return rc;
   return bits ? sf_error(m, bits) : INFLX_OK;
+}
+
+// ... and an integrating call, one that reports a status per lane.  The adaptive step control recovers from a trial step whose stages
+// left a function's domain (inflx_bg_step_taken: a non-finite trial is retried at a fifth of the step): the lane goes on inside the
+// domain and every state it stores is finite, but the trial has set the bit.  So a set word fails the call only when a lane of it
+// stopped INFLX_EOM_NONFINITE (`nonfinite`); otherwise the word is cleared and the call succeeds.
+int sf_verdict_lanes(inflx_model* m, bool nonfinite) {
+  if (m->sf_words.empty() || m->sf_policy != INFLX_SF_FAIL) return INFLX_OK;
+  unsigned bits = 0;
+  const int rc = sf_collect(m, true, &bits);
+  if (rc) return rc;
+  return bits && nonfinite ? sf_error(m, bits, /*lanes=*/true) : INFLX_OK;
 }
 
 // ---- kernel groups ----------------------------------------------------------------------------------------------------------
@@ -3142,6 +3162,7 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
   const CompanionSlot& bg = m->companion[kObjBackground];
   hipFunction_t advance = bg.fn[kBgAdvance + 2 * (method == INFLX_EOM_RKF ? 1 : 0) + (store ? 1 : 0)];
 
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxBgArgs a;
@@ -3227,6 +3248,7 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
       status[c0 + l] = (int8_t)hc[INFLX_BG_CARRY_STATUS * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
       if (efolds) efolds[c0 + l] = hc[INFLX_BG_CARRY_NEND * n + l];
       if (last_row) last_row[c0 + l] = (int64_t)hc[INFLX_BG_CARRY_LAST_ROW * n + l];
       if (final_only) {
@@ -3236,7 +3258,7 @@ int solve_eom_passes(inflx_model* m, hipStream_t s, const double* p, size_t P, s
       }
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // namespace
@@ -3300,6 +3322,7 @@ int inflx_solve_eom_to_efolds(inflx_model* m, const double* p, size_t P, size_t 
   const CompanionSlot& bg = m->companion[kObjBackground];
   hipFunction_t advance = bg.fn[kBgTarget + (method == INFLX_EOM_RKF ? 1 : 0)];
 
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxBgArgs a;
@@ -3326,6 +3349,7 @@ int inflx_solve_eom_to_efolds(inflx_model* m, const double* p, size_t P, size_t 
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
       status[c0 + l] = (int8_t)hc[INFLX_BG_CARRY_STATUS * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
       if (efolds) efolds[c0 + l] = hc[INFLX_BG_CARRY_NEND * n + l];
       if (eps_h) eps_h[c0 + l] = hc[INFLX_BG_CARRY_EPS * n + l];
       if (states)
@@ -3333,7 +3357,7 @@ int inflx_solve_eom_to_efolds(inflx_model* m, const double* p, size_t P, size_t 
       if (t) t[c0 + l] = hc[INFLX_BG_CARRY_T * n + l];
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, const double* samples, size_t S,
@@ -3364,6 +3388,7 @@ int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_
   const CompanionSlot& bg = m->companion[kObjBackground];
   hipFunction_t advance = bg.fn[kBgSampled + (method == INFLX_EOM_RKF ? 1 : 0)];
 
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxBgArgs a;
@@ -3395,11 +3420,12 @@ int inflx_solve_eom_sampled(inflx_model* m, const double* p, size_t P, size_t n_
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
       status[c0 + l] = (int8_t)hc[INFLX_BG_CARRY_STATUS * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
       if (efolds) efolds[c0 + l] = hc[INFLX_BG_CARRY_NEND * n + l];
       if (n_stored) n_stored[c0 + l] = (uint32_t)hc[INFLX_BG_CARRY_LAST_ROW * n + l];
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // extern "C"
@@ -3570,6 +3596,7 @@ int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n
   const CompanionSlot& tr = m->companion[kObjTransfer];
   hipFunction_t advance = tr.fn[kLaneAdvance + (method == INFLX_EOM_RKF ? 1 : 0)];
 
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxTrArgs a;
@@ -3602,6 +3629,7 @@ int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
       status[c0 + l] = (int8_t)hc[(INFLX_TR_CARRY_STATUS - INFLX_TR_CARRY_NEND) * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
       if (efolds) efolds[c0 + l] = hc[l];
       if (n_stored) n_stored[c0 + l] = (uint32_t)hc[(INFLX_TR_CARRY_CURSOR - INFLX_TR_CARRY_NEND) * n + l];
       if (ends) {
@@ -3610,7 +3638,7 @@ int inflx_transfer_functions(inflx_model* m, const double* p, size_t P, size_t n
       }
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // extern "C"
@@ -3676,6 +3704,7 @@ int run_mode_lanes(inflx_model* m, int method, const double* p, size_t P, size_t
   }
   std::vector<double> host_carry(nc_max * kBack);
 
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     typename L::Args a;
@@ -3718,10 +3747,11 @@ int run_mode_lanes(inflx_model* m, int method, const double* p, size_t P, size_t
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
       status[c0 + l] = (int8_t)hc[(L::kCarryStatus - L::kCarryNend) * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
       if (efolds) efolds[c0 + l] = hc[l];
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // namespace
@@ -3810,6 +3840,7 @@ int inflx_delta_n(inflx_model* m, const double* p, size_t P, size_t n_p, const d
   // the workgroups of a launch over `lanes` lanes
   auto grid_of = [](size_t lanes) { return (unsigned)((lanes + INFLX_DN_THREADS - 1) / INFLX_DN_THREADS); };
   std::vector<double> host_status(nb_max), host_surface(2 * nb_max);
+  bool nonfinite = false;  // a stencil of the call reports INFLX_EOM_NONFINITE
 
   for (size_t c0 = 0; c0 < B; c0 += nb_max) {
     const size_t nb = std::min(nb_max, B - c0);
@@ -3867,13 +3898,14 @@ int inflx_delta_n(inflx_model* m, const double* p, size_t P, size_t n_p, const d
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t l = 0; l < nb; ++l) {
       status[c0 + l] = (int32_t)host_status[l];
+      nonfinite |= status[c0 + l] % 16 == INFLX_EOM_NONFINITE;  // (s of s + 16 m: the status of the lowest member that failed)
       if (surface) {
         surface[c0 + l] = host_surface[l];
         surface[B + c0 + l] = h_end ? std::numeric_limits<double>::quiet_NaN() : host_surface[nb + l];
       }
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // extern "C"
@@ -3964,7 +3996,9 @@ int inflx_stochastic_efolds(inflx_model* m, const double* p, size_t P, size_t n_
       }
     }
   }
-  return sf_verdict(m);
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE: the moments count the lanes of every status
+  for (size_t b = 0; b < B; ++b) nonfinite |= moments[(size_t)(INFLX_ST_OUT_COUNT_PLANE + INFLX_EOM_NONFINITE) * B + b] > 0.0;
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // extern "C"
@@ -4097,7 +4131,9 @@ int inflx_stochastic_distribution(inflx_model* m, const double* p, size_t P, siz
     HIP_TRY(hipMemcpyAsync(counts + c0 * INFLX_PD_STATUSES, d_counts, nb * INFLX_PD_STATUSES * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
-  return sf_verdict(m);
+  bool nonfinite = false;  // a realisation of the call stopped INFLX_EOM_NONFINITE
+  for (size_t b = 0; b < B; ++b) nonfinite |= counts[b * INFLX_PD_STATUSES + INFLX_EOM_NONFINITE] != 0;
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // extern "C"
@@ -4135,6 +4171,7 @@ int inflx_solve_eom_crossings(inflx_model* m, const double* p, size_t P, size_t 
   const CompanionSlot& hx = m->companion[kObjCrossing];
   hipFunction_t advance = hx.fn[kHxAdvance + (method == INFLX_EOM_RKF ? 1 : 0)];
 
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxHxArgs a;
@@ -4167,13 +4204,14 @@ int inflx_solve_eom_crossings(inflx_model* m, const double* p, size_t P, size_t 
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
       status[c0 + l] = (int8_t)hc[INFLX_HX_CARRY_STATUS * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
       if (efolds) efolds[c0 + l] = hc[INFLX_HX_CARRY_NEND * n + l];
       const uint32_t before = (uint32_t)hc[INFLX_HX_CARRY_BEFORE * n + l];
       if (n_before) n_before[c0 + l] = before;
       if (n_stored) n_stored[c0 + l] = (uint32_t)hc[INFLX_HX_CARRY_CURSOR * n + l] - before;
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 int inflx_inflation_end(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, size_t B, size_t max_steps, int method, double max_err, double dt,
@@ -4197,6 +4235,7 @@ int inflx_inflation_end(inflx_model* m, const double* p, size_t P, size_t n_p, c
   const CompanionSlot& hx = m->companion[kObjCrossing];
   hipFunction_t advance = hx.fn[kHxEnd + (method == INFLX_EOM_RKF ? 1 : 0)];
 
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
   for (size_t c0 = 0; c0 < B; c0 += nc_max) {
     const size_t n = std::min(nc_max, B - c0);
     InflxHxArgs a;
@@ -4219,13 +4258,14 @@ int inflx_inflation_end(inflx_model* m, const double* p, size_t P, size_t n_p, c
     const double* hc = host_carry.data();
     for (size_t l = 0; l < n; ++l) {
       status[c0 + l] = (int8_t)hc[INFLX_HX_CARRY_STATUS * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
       if (eps_h) eps_h[c0 + l] = hc[INFLX_HX_CARRY_EPS * n + l];
       if (states)
         for (int c = 0; c < 6; ++c) states[(c0 + l) * 6 + c] = hc[(size_t)(INFLX_HX_CARRY_Y + c) * n + l];
       if (t) t[c0 + l] = hc[INFLX_HX_CARRY_T * n + l];
     }
   }
-  return sf_verdict(m);
+  return sf_verdict_lanes(m, nonfinite);
 }
 
 }  // extern "C"

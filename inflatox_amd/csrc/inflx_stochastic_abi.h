@@ -17,6 +17,7 @@
 
 #define INFLX_ST_THREADS 256
 #define INFLX_ST_OUT_PLANES 12     // csrc/inflx_stochastic.h InflxStOut: mean, m2, m3, m4, min, max, lanes per status 0..5
+#define INFLX_ST_OUT_COUNT_PLANE 6  // the first of the six planes of lanes per status: InflxStOut's INFLX_ST_OUT_COUNTS
 #define INFLX_ST_SAMPLE_PLANES 7   // N, phi^0, phi^1, chi^0, chi^1, H, status of every lane
 #define INFLX_ST_MAX_REALISATIONS (1u << 20)
 

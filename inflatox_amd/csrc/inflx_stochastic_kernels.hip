@@ -40,6 +40,7 @@ static_assert(INFLX_DIM == 2, "the stochastic kernels need a two-field model");
 #include "inflx_stochastic_abi.h"
 
 static_assert(INFLX_ST_OUT_PLANES == INFLX_ST_NOUT, "csrc/inflx_stochastic.h and csrc/inflx_stochastic_abi.h disagree");
+static_assert(INFLX_ST_OUT_COUNT_PLANE == INFLX_ST_OUT_COUNTS, "csrc/inflx_stochastic.h and csrc/inflx_stochastic_abi.h disagree");
 static_assert(INFLX_ST_THREADS == 256, "inflx_st_reduce merges four wavefronts");
 
 #define INFLX_EXPORT extern "C" __device__ __attribute__((used, visibility("default")))

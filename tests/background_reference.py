@@ -230,7 +230,8 @@ class BackgroundTwin:
         header_text = artifact._build[0]
         eom_text = artifact.eom_header_text()
         background_h = open(os.path.join(ROOT, "inflatox_amd", "csrc", "inflx_background.h")).read()
-        tag = hashlib.sha1((header_text + eom_text + background_h + contract).encode()).hexdigest()[:16]
+        twin_cpp = open(os.path.join(HERE, "background_twin.cpp")).read()
+        tag = hashlib.sha1((header_text + eom_text + background_h + twin_cpp + contract).encode()).hexdigest()[:16]
         d = os.path.join(tempfile.gettempdir(), "inflx_background_twin")
         os.makedirs(d, exist_ok=True)
         hdr, eom_hdr, so = (os.path.join(d, f"{tag}{s}") for s in (".h", ".eom.h", ".so"))
@@ -248,6 +249,12 @@ class BackgroundTwin:
         self.lib = C.CDLL(so)
         self.lib.twin_eom.argtypes = [_DP, _DP, C.c_size_t, _DP]
         self.lib.twin_solve.argtypes = [_DP, _DP, C.c_size_t, C.c_uint, C.c_int, C.c_double, C.c_double, C.c_int, _DP, _DP]
+        self.lib.twin_sf_status_take.restype = C.c_uint
+
+    def sf_status_take(self) -> int:
+        """The bits (csrc/inflx_sf.h: INFLX_SF_EDOM = 1, INFLX_SF_EDECLINED = 2) the model's special functions have set in this build
+        since they were last read; reading clears them."""
+        return int(self.lib.twin_sf_status_take())
 
     def eom(self, p, pts):
         p = np.ascontiguousarray(p, dtype=np.float64)

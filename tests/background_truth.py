@@ -5,8 +5,9 @@ restatement's model callable.  What is here does not.  ``euler_lagrange_eom`` de
 L = G_ab chi^a chi^b / 2 - V without the connection, the inverse metric or anything of inflatox_amd.symbolic;
 ``truth_trajectory`` integrates them with scipy's DOP853 at tolerances far below every bound that is asserted against it
 (tests/test_background_truth.py validates it against 30-digit Taylor integration).  The model zoo is the fuzzed models of
-tests/test_model_fuzz.py (diagonal metrics that depend on either field) and two hand-written models with G_01 != 0; ``batch``
-gives each a seeded set of initial states and per-lane parameter rows.
+tests/test_model_fuzz.py (diagonal metrics that depend on either field), two hand-written models with G_01 != 0 and the models of
+``special_model``, which call Bessel and hypergeometric functions (``Compiler(link_gsl=True)``); ``batch`` gives each a seeded set
+of initial states and per-lane parameter rows.
 """
 
 from __future__ import annotations
@@ -130,6 +131,8 @@ class ZooModel(NamedTuple):
     model: object
     cse: bool
     box: tuple  # (x0 min, x0 max, x1 min, x1 max): the model's extent
+    gsl: bool = False  # the model calls special functions: Compiler(link_gsl=True), truths through scipy / mpmath
+    par_ranges: tuple = ()  # ((printed name, min, max), ...) of the parameters that are not drawn from [0.5, 1.8]
 
 
 def _build(name, G, V):
@@ -158,14 +161,67 @@ def nondiagonal_model(name):
 
 NONDIAGONAL = ("skew", "shear")
 
+NU = sp.Symbol("nu")
+
+
+@functools.lru_cache(maxsize=None)
+def special_model(name):
+    """Models that call the special functions of csrc/inflx_sf.h.  The equations of motion, the kinematics and the noise take first
+    derivatives, which shift a Bessel order by one and both hypergeometric parameters by one; the masses take second ones.
+
+    ``bessel_skew``: ``skew`` with I_0 in the metric -- it reaches the connection, the Ricci scalar and the noise's Cholesky factor --
+    and J_0 and K_nu in the potential; nu in [2, 3.5], so that every shifted order nu - 2 .. nu + 2 stays >= 0, and the arguments
+    x, x / 2 and x + 1 are positive on the box.  det G >= I_0(0.15) + b - a^2 / 9 > 1.1; V >= a (3 + J_0(2)) > 1.6.
+    ``kummer_curved``: a curved diagonal metric and a potential with 1F1(a; c; -x / 2) and 2F1(a, 1/2; c; y / 3), a and c the model's
+    parameters: c > 0 is never a non-positive integer, however often it is shifted up, and y / 3 stays in (-1/3, 1/2), inside
+    2F1's -1 <= z < 1.  tests/test_background_special.py establishes V >= 0.25 over the box and the domain along the truth runs.
+    ``j52_wall``: V = b + a J_5/2(phi) - c phi on a flat field space, J_nu defined for phi >= 0 only: a field that rolls towards
+    phi = 0 under the slope -c meets the domain's edge.  For the status tests alone (``wall_lanes``); it has no box to draw from."""
+    a, b, c = PARAMS
+    if name == "bessel_skew":
+        off = a * sp.sin(x) / 3
+        G = [[1 + y**2, off], [off, sp.besseli(0, x / 2) + b]]
+        V = a * (3 + sp.besselj(0, x) + y**2 / 3) + b * sp.besselk(NU, x + 1) / 2
+        return ZooModel(name, _build(name, G, V), False, (0.3, 2.0, -1.0, 1.5), True, (("nu", 2.0, 3.5),))
+    if name == "kummer_curved":
+        G = [[sp.cosh(y / 2) ** 2, 0], [0, 1 + b * x**2 / 4]]
+        V = b * (4 + sp.hyper((a,), (c,), -x / 2) + y**2 / 3) + sp.hyper((a, sp.Rational(1, 2)), (c,), y / 3) / 2
+        return ZooModel(name, _build(name, G, V), False, (0.3, 2.0, -1.0, 1.5), True)
+    if name == "j52_wall":
+        V = b + a * sp.besselj(sp.Rational(5, 2), x) - c * x
+        return ZooModel(name, _build(name, [[1, 0], [0, 1]], V), False, (0.0, 1.0, -1.0, 1.0), True)
+    raise KeyError(name)
+
+
+SPECIAL_VALUE_MODELS = ("bessel_skew", "kummer_curved")
+
+
+def _hyper_scipy(ap, bq, z):
+    """sympy's ``hyper`` for scipy: 1F1 and 2F1, the two that the special models use"""
+    from scipy import special
+
+    if (len(ap), len(bq)) == (1, 1):
+        return special.hyp1f1(ap[0], bq[0], z)
+    if (len(ap), len(bq)) == (2, 1):
+        return special.hyp2f1(ap[0], ap[1], bq[0], z)
+    raise NotImplementedError((ap, bq))
+
+
+def float_modules(z):
+    """``modules`` of a float64 ``point_function`` of a zoo model: the math module, or scipy for the special functions"""
+    return [{"hyper": _hyper_scipy}, "scipy", "numpy"] if z.gsl else "math"
+
 
 @functools.lru_cache(maxsize=None)
 def zoo_model(name):
-    """``"fuzz<seed>"``: ``random_model(seed)`` of tests/test_model_fuzz.py; ``"skew"`` / ``"shear"``: the non-diagonal models."""
+    """``"fuzz<seed>"``: ``random_model(seed)`` of tests/test_model_fuzz.py; ``"skew"`` / ``"shear"``: the non-diagonal models;
+    ``"bessel_skew"`` / ``"kummer_curved"`` / ``"j52_wall"``: the models with special functions."""
     if name.startswith("fuzz"):
         model, _args, ext, cse = random_model(int(name[4:]))
         return ZooModel(name, model, cse, tuple(ext))
-    return nondiagonal_model(name)
+    if name in NONDIAGONAL:
+        return nondiagonal_model(name)
+    return special_model(name)
 
 
 GPU_MODELS = tuple(f"fuzz{s}" for s in GPU_FUZZ_SEEDS) + NONDIAGONAL
@@ -179,7 +235,7 @@ def host_artifact(name):
     from inflatox_amd.compiler import CompilationArtifact
 
     z = zoo_model(name)
-    comp = Compiler(z.model, silent=True, cse=z.cse)
+    comp = Compiler(z.model, silent=True, cse=z.cse, link_gsl=z.gsl)
     header = comp._generate_hip_header()
     art = CompilationArtifact(comp.symbol_dict, f"/nonexistent/{name}.hsaco", 2, len(comp.symbol_dict) - 2, auto_cleanup=False)
     art._build = (header, [], "")
@@ -192,7 +248,7 @@ def device_artifact(name):
     from inflatox_amd import Compiler
 
     z = zoo_model(name)
-    return Compiler(z.model, silent=True, cse=z.cse).compile()
+    return Compiler(z.model, silent=True, cse=z.cse, link_gsl=z.gsl).compile()
 
 
 V_MIN, VELOCITY, B_MAX = 0.25, 0.3, 257
@@ -221,7 +277,10 @@ def _batch(name, draw):
     x0, x1, y0, y1 = z.box
     init = np.stack([rng.uniform(x0, x1, n), rng.uniform(y0, y1, n), rng.uniform(-VELOCITY, VELOCITY, n), rng.uniform(-VELOCITY, VELOCITY, n)], axis=1)
     pars = rng.uniform(0.5, 1.8, (n, art.n_parameters))
-    potential = point_function(z.model.coordinates, z.model.coordinate_tangents, [z.model.potential], art.symbol_dictionary)
+    for par, lo, hi in z.par_ranges:  # the same draw, carried to the parameter's own range
+        k = int(art.symbol_dictionary[par][5:-1])
+        pars[:, k] = lo + (pars[:, k] - 0.5) / 1.3 * (hi - lo)
+    potential = point_function(z.model.coordinates, z.model.coordinate_tangents, [z.model.potential], art.symbol_dictionary, float_modules(z))
     keep = [k for k in range(n) if potential(*init[k], pars[k])[0] >= V_MIN][:B_MAX]
     assert len(keep) == B_MAX, (name, len(keep))
     init, pars = np.ascontiguousarray(init[keep]), np.ascontiguousarray(pars[keep])
@@ -233,7 +292,8 @@ def _batch(name, draw):
 @functools.lru_cache(maxsize=None)
 def truth_rhs(name):
     """eom(x0, x1, xd0, xd1, p) of the Euler-Lagrange derivation in float64, parameters in the artefact's slots."""
-    return truth_functions(zoo_model(name).model, host_artifact(name).symbol_dictionary)
+    z = zoo_model(name)
+    return truth_functions(z.model, host_artifact(name).symbol_dictionary, float_modules(z))
 
 
 def bound(eom, p):

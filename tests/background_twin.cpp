@@ -42,6 +42,14 @@ void twin_eom(const double* p, const double* pts, size_t n, double* out) {
   for (size_t k = 0; k < n; ++k) inflx_eom_point(pts[4 * k], pts[4 * k + 1], pts[4 * k + 2], pts[4 * k + 3], p, out + 4 * k);
 }
 
+// the status word the model's special functions leave their domain notes in (csrc/inflx_sf.h: the host word of this library);
+// reading clears it, as sf_status_take of tests/sf_host.cpp does
+unsigned twin_sf_status_take() {
+  const unsigned v = inflx_sf_status_host;
+  inflx_sf_status_host = 0u;
+  return v;
+}
+
 // One trajectory: rows (rows, 7) = y[0..5], t (NaN after the lane stopped); meta = status, N_end, last_row, accepted steps
 void twin_solve(const double* p, const double* init, size_t rows, unsigned substeps, int method, double max_err, double dt, int stop_at_end,
                 double* out, double* meta) {

@@ -609,6 +609,33 @@ def parity_cases():
     yield "skew", bt.host_artifact("skew"), z.model, np.array([1.0, 1.2, 0.8])[: bt.host_artifact("skew").n_parameters], pts
 
 
+# ... and on a model with special functions (background_truth.special_model): I_0 in the metric reaches the kicks' Cholesky factor
+# and I_1 the drift; three points of the box, per-point parameter rows, 200 steps like ``skew``
+SPECIAL_MODEL = "bessel_skew"
+SPECIAL_POINTS = np.array([[1.2, 0.3, -0.1, 0.05], [0.8, -0.5, 0.1, -0.05], [1.7, 1.0, -0.05, 0.02]])
+SPECIAL_PARS = np.array([[1.0, 1.2, 2.4], [0.7, 1.6, 3.1], [1.5, 0.6, 2.0]])  # a, b, nu
+SPECIAL_STEPS = 200
+
+
+def special_run(run, solver):
+    """``run(p, pts, R, **kw)`` -- a twin's ``run`` or the device's -- on the special-function case"""
+    return run(SPECIAL_PARS, SPECIAL_POINTS, PARITY_R, seed=PARITY_SEED, noise_scale=PARITY_SCALE, max_steps=SPECIAL_STEPS, solver=solver, dt=PARITY_DT)
+
+
+def measure_d_special():
+    """``measure_d`` on the special-function case: {solver: worst difference}"""
+    import background_truth as bt
+
+    art = bt.host_artifact(SPECIAL_MODEL)
+    d = {solver: lane_difference(*[special_run(StochasticTwin(art, contract=c).run, solver) for c in ("off", "fast")]) for solver in ("rk4", "rkf")}
+    d["worst"] = max(d.values())
+    return d
+
+
+def bound_special():
+    return 1e-10 + 2.0 * recorded()["d_" + SPECIAL_MODEL]["worst"]
+
+
 def measure_d():
     """the twin with FMA contraction against the twin without, over the lane-by-lane cases: {case/solver: worst difference}"""
     d = {}
@@ -627,6 +654,7 @@ if __name__ == "__main__":
     sys.path.insert(0, ROOT)
     result = recorded() if os.path.exists(PROFILE) else {}
     result["d"] = measure_d()
+    result["d_" + SPECIAL_MODEL] = measure_d_special()
     result["d_what"] = ("worst absolute lane difference (N_end and the five state components) between the host twin built with -ffp-contract=fast -mfma and with "
                         "-ffp-contract=off, fixed dt, same Philox stream; tests assert 1e-10 + 2 x worst")  # fmt: skip
     with open(PROFILE, "w") as fh:

@@ -388,6 +388,9 @@ CASES = [
     (lambda: bg.pivot_observables_map(A, P, SS, 3, 2, -61.0, 0.0, 0.0), ValueError, "N_sub must be finite and > 0 (got 0.0)"),  # two faults: N_sub before dlnk
     (lambda: bg.pivot_observables_map(A, P, [0.0, 1.0], 3, 2, -61.0, 0.0), ValueError, "dlnk must be finite and > 0 (got 0.0)"),  # two faults: dlnk before start_stop
     (lambda: bg.pivot_observables_map(A, P63, SS, 3, 2, math.nan), ValueError, "A must be finite"),  # two faults: A before the parameter rows
+    # ---- the special-function policy: the words of GeneralisedAL(..., sf_errors=), refused before the handle is opened
+    (lambda: bg.set_sf_errors(A, "loud"), ValueError, "sf_errors must be \"raise\" or \"nan\" (got 'loud')"),
+    (lambda: bg.set_sf_errors(A, None), ValueError, "sf_errors must be \"raise\" or \"nan\" (got None)"),
 ]
 # fmt: on
 
