@@ -686,5 +686,7 @@ int inflx_mode_spectra(inflx_model* model, const double* p, size_t P, size_t n_p
 #include "inflx_hip_distribution.h"
 /* horizon crossings (the state where ln(a H) reaches given values, the located end of inflation): likewise */
 #include "inflx_hip_crossing.h"
+/* reheating (trajectories whose fields decay into radiation, to the point where the radiation dominates): likewise */
+#include "inflx_hip_reheating.h"
 
 #endif /* INFLX_HIP_H */

@@ -177,6 +177,13 @@ CROSSING_SIGNATURES = {
         [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _SIZE, _SIZE, C.c_int, C.c_double, C.c_double, _DP, _DP, _DP, C.POINTER(C.c_int8)],
     ),
 }
+# ... and for include/inflx_hip_reheating.h
+REHEATING_SIGNATURES = {
+    "inflx_reheating": (
+        C.c_int,
+        [C.c_void_p, _DP, _SIZE, _SIZE, _DP, _DP, _DP, _SIZE, C.c_double, _SIZE, C.c_int, C.c_double, C.c_double, _DP, _DP, _DP, C.POINTER(C.c_int8)],
+    ),
+}
 PD_MAX_REALISATIONS = (1 << 32) - 1
 PD_MAX_BINS = 1 << 20
 PD_MAX_LANES_PER_POINT = 1 << 20
@@ -200,7 +207,7 @@ _lib = None
 def build_library(force: bool = False) -> str:
     """Compile ``csrc/inflx_hip.cpp`` into ``libinflx_hip.so`` in-tree (hipcc, host code only)."""
     src = os.path.join(_PKG, "csrc", "inflx_hip.cpp")
-    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h"), os.path.join(_PKG, "csrc", "inflx_stochastic_abi.h"), os.path.join(_REPO, "include", "inflx_hip_stochastic.h"), os.path.join(_PKG, "csrc", "inflx_distribution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_distribution.h"), os.path.join(_PKG, "csrc", "inflx_crossing_abi.h"), os.path.join(_REPO, "include", "inflx_hip_crossing.h")]
+    deps = [src, os.path.join(_PKG, "csrc", "inflx_kernel_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_abi.h"), os.path.join(_PKG, "csrc", "inflx_background_rows.h"), os.path.join(_PKG, "csrc", "inflx_background_passes.h"), os.path.join(_PKG, "csrc", "inflx_kinematics_abi.h"), os.path.join(_PKG, "csrc", "inflx_masses_abi.h"), os.path.join(_PKG, "csrc", "inflx_transfer_abi.h"), os.path.join(_PKG, "csrc", "inflx_modes_abi.h"), os.path.join(_PKG, "csrc", "inflx_tensor_abi.h"), os.path.join(_PKG, "csrc", "inflx_deltan_abi.h"), os.path.join(_REPO, "include", "inflx_hip.h"), os.path.join(_REPO, "include", "inflx_hip_deltan.h"), os.path.join(_PKG, "csrc", "inflx_evolution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_evolution.h"), os.path.join(_PKG, "csrc", "inflx_stochastic_abi.h"), os.path.join(_REPO, "include", "inflx_hip_stochastic.h"), os.path.join(_PKG, "csrc", "inflx_distribution_abi.h"), os.path.join(_REPO, "include", "inflx_hip_distribution.h"), os.path.join(_PKG, "csrc", "inflx_crossing_abi.h"), os.path.join(_REPO, "include", "inflx_hip_crossing.h"), os.path.join(_PKG, "csrc", "inflx_reheating_abi.h"), os.path.join(_REPO, "include", "inflx_hip_reheating.h")]
     stale = force or not os.path.exists(LIB_PATH) or any(os.path.getmtime(d) > os.path.getmtime(LIB_PATH) for d in deps)
     if stale:
         from .compiler import hipcc_path
@@ -257,7 +264,7 @@ def load_library():
         _preload_hip_runtime()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (*SIGNATURES.items(), *DELTAN_SIGNATURES.items(), *EVOLUTION_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items(),
-                                  *DISTRIBUTION_SIGNATURES.items(), *CROSSING_SIGNATURES.items()):
+                                  *DISTRIBUTION_SIGNATURES.items(), *CROSSING_SIGNATURES.items(), *REHEATING_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -637,6 +644,30 @@ class InflatoxDevLib:
             )
         )  # fmt: skip
         return states, t, eps_h, status
+
+    # ---- reheating (include/inflx_hip_reheating.h: inflx_reheating) ------
+    def reheating(self, p, init, gamma, rho_r0, omega_r: float, max_steps: int, method: int, max_err: float, dt: float):
+        """B trajectories from ``init`` (B,4) whose fields decay at the rates ``gamma`` (B,) into radiation of the initial density
+        ``rho_r0`` (B,), each until rho_r / (3 H^2) reaches ``omega_r``.  Returns (states (B, 7): y[0..5] and rho_r where every
+        trajectory stopped -- the located state for status 10 --, t, H_0, status (int8)).  The reheating object must be in place
+        (``CompilationArtifact.ensure_reheating``)."""
+        init = _f64(init, "init")
+        p, P = _rows(p)
+        gamma = _f64(gamma, "gamma")
+        rho_r0 = _f64(rho_r0, "rho_r0")
+        B = init.shape[0]
+        _lanes(gamma, "gamma", B)
+        _lanes(rho_r0, "rho_r0", B)
+        states = np.empty((B, 7))
+        t, h_start = np.empty(B), np.empty(B)
+        status = np.empty(B, dtype=np.int8)
+        _check(
+            self._lib.inflx_reheating(
+                self._h, _ptr(p), P, self.n_parameters, _ptr(init), _ptr(gamma), _ptr(rho_r0), B, float(omega_r), int(max_steps), int(method), float(max_err),
+                float(dt), _ptr(states), _ptr(t), _ptr(h_start), _typed(status, C.c_int8),
+            )
+        )  # fmt: skip
+        return states, t, h_start, status
 
     # ---- trajectory kinematics (include/inflx_hip.h: inflx_kinematics) --------------------------
     def kinematics(self, p, states: np.ndarray, n: int, ld: int, traj_len: int = 1) -> np.ndarray:

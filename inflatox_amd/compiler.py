@@ -218,7 +218,7 @@ class CompilationArtifact:
         self._build = None  # (header text, final hipcc options, content tag): what ensure_group compiles a further group from
         self._group_paths = {}
         self._eom_recipe = None  # (model, parameter slots, cse, max_cses): what ensure_background emits the EoM header from
-        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" / "stochastic" / "distribution" / "crossing" -> the object beside shared_object_path, once built
+        self._companion_paths = {}  # "background" / "kinematics" / "masses" / "transfer" / "modes" / "tensor" / "deltan" / "evolution" / "stochastic" / "distribution" / "crossing" / "reheating" -> the object beside shared_object_path, once built
         _ARTEFACTS[os.path.abspath(shared_object_path)] = self
 
     def ensure_group(self, group: str) -> str | None:
@@ -440,6 +440,16 @@ class CompilationArtifact:
         Like the other ten companion objects it lies outside the kernel groups, and none of them is involved."""
         return self._ensure_companion("crossing", _CROSSING_SOURCES, "hx{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "hx{key}.eom.h", self.eom_header_text())])
 
+    def ensure_reheating(self) -> str:
+        """Extension: build the reheating code object of this model -- the kernels of ``inflatox_amd.reheating.reheating``
+        (csrc/inflx_reheating_kernels.hip) -- and return its path, ``shared_object_path + ".reheating"``, where ``libinflx_hip.so``
+        looks for it.  One hipcc step on first use from the core object's header and options plus the header of the equations of
+        motion, cached as ``<tag>.rh<hash>.hsaco`` (the hash covers the generated header and ``_REHEATING_SOURCES``, code only --
+        csrc/inflx_background.h among them, whose step control and dense output the kernels reuse); the object carries the core
+        object's ``MODEL_TAG`` and a layout word of its own (``INFLX_RH_ABI``).  Like the other eleven companion objects it lies
+        outside the kernel groups, and none of them is involved."""
+        return self._ensure_companion("reheating", _REHEATING_SOURCES, "rh{key}.hsaco", lambda: [("INFLX_EOM_HEADER", "rh{key}.eom.h", self.eom_header_text())])
+
     def ensure_rowpass(self) -> str | None:
         """Extension: build the row-pass code object of a model none of whose values depends on the second field -- the per-row
         evaluation of the row-broadcast sweeps (csrc/inflx_rowpass_kernels.hip) -- and return its path, ``shared_object_path +
@@ -575,6 +585,8 @@ _DISTRIBUTION_SOURCES = ("inflx_distribution_kernels.hip", "inflx_distribution.h
                          "inflx_background.h", "inflx_background_abi.h")  # fmt: skip
 _CROSSING_SOURCES = ("inflx_crossing_kernels.hip", "inflx_crossing.h", "inflx_crossing_abi.h", "inflx_deltan.h", "inflx_background.h",
                      "inflx_background_abi.h")  # fmt: skip
+_REHEATING_SOURCES = ("inflx_reheating_kernels.hip", "inflx_reheating.h", "inflx_reheating_abi.h", "inflx_deltan.h", "inflx_background.h",
+                      "inflx_background_abi.h")  # fmt: skip
 _ROWPASS_SOURCES = ("inflx_rowpass_kernels.hip", "inflx_rowpass_abi.h")
 
 

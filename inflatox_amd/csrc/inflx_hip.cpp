@@ -53,6 +53,7 @@
 #include "inflx_stochastic_abi.h"
 #include "inflx_distribution_abi.h"
 #include "inflx_crossing_abi.h"
+#include "inflx_reheating_abi.h"
 
 namespace {
 
@@ -373,7 +374,7 @@ struct TableRing {
 
 // The code objects beside the core object that the background solver's families live in (kCompanions describes them), and what a
 // handle holds of one: its module and its kernels, in the order of the description's names.
-enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kObjStochastic, kObjDistribution, kObjCrossing, kCompanionCount };
+enum Companion { kObjBackground, kObjKinematics, kObjMasses, kObjTransfer, kObjModes, kObjTensor, kObjDeltan, kObjEvolution, kObjStochastic, kObjDistribution, kObjCrossing, kObjReheating, kCompanionCount };
 constexpr int kCompanionKernels = 10;  // the most kernels of one object (background)
 struct CompanionSlot {
   hipModule_t module = nullptr;
@@ -2915,7 +2916,7 @@ int inflx_sweep_allgather_multi_ex(inflx_multi* mm, int op, const double* p, siz
 }  // extern "C"
 
 // ---- the background solver: what its families share ---------------------------------------------------------------------------
-// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution, stochastic e-folds, first-passage histograms, horizon crossings -- has its kernels in
+// Every family -- trajectories, kinematics, masses, transfer functions, mode functions, tensor modes, delta-N, mode evolution, stochastic e-folds, first-passage histograms, horizon crossings, reheating -- has its kernels in
 // a code object of its own beside the core object, `<artefact>.<suffix>`, which CompilationArtifact.ensure_<suffix>() builds.
 // kCompanions has one constant description per object: the words of its messages, its layout word, its kernels.  need_companion
 // loads any of them into its slot of the handle on first use, and a call site names a kernel by its family's index below.  The
@@ -2936,6 +2937,7 @@ static_assert(kAbiMajor == INFLX_EV_DEFAULT_ABI_MAJOR, "an evolution object repo
 static_assert(kAbiMajor == INFLX_ST_DEFAULT_ABI_MAJOR, "a stochastic object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_PD_DEFAULT_ABI_MAJOR, "a distribution object reports the core object's ABI major: change both together");
 static_assert(kAbiMajor == INFLX_HX_DEFAULT_ABI_MAJOR, "a crossing object reports the core object's ABI major: change both together");
+static_assert(kAbiMajor == INFLX_RH_DEFAULT_ABI_MAJOR, "a reheating object reports the core object's ABI major: change both together");
 
 struct CompanionDesc {
   const char* suffix;      // the file is `<artefact>.<suffix>` and CompilationArtifact.ensure_<suffix>() builds it
@@ -2954,6 +2956,7 @@ enum DnKernel { kDnInit, kDnReduce, kDnEnd /* + method: phase A */, kDnSurface =
 enum StKernel { kStInit, kStReduce, kStAdvance /* + method */ };
 enum PdKernel { kPdInit, kPdAdvance /* + method */ };
 enum HxKernel { kHxInit, kHxAdvance /* + method: crossings */, kHxEnd = 3 /* + method: the end of inflation */ };
+enum RhKernel { kRhInit, kRhAdvance /* + method */ };
 const CompanionDesc kCompanions[kCompanionCount] = {
     {"background", "background kernels", "are", "inflatox_amd.background", "INFLX_BG_ABI", INFLX_BG_ABI_VERSION,
      {"inflx_bg_init", "inflx_bg_rows_transpose", "inflx_bg_advance_rk4_final", "inflx_bg_advance_rk4_rows", "inflx_bg_advance_rkf_final", "inflx_bg_advance_rkf_rows",
@@ -2976,6 +2979,8 @@ const CompanionDesc kCompanions[kCompanionCount] = {
      {"inflx_pd_init", "inflx_pd_advance_rk4", "inflx_pd_advance_rkf"}},
     {"crossing", "crossing kernels", "are", "inflatox_amd.background.horizon_crossings", "INFLX_HX_ABI", INFLX_HX_ABI_VERSION,
      {"inflx_hx_init", "inflx_hx_advance_rk4", "inflx_hx_advance_rkf", "inflx_hx_end_rk4", "inflx_hx_end_rkf"}},
+    {"reheating", "reheating kernels", "are", "inflatox_amd.reheating.reheating", "INFLX_RH_ABI", INFLX_RH_ABI_VERSION,
+     {"inflx_rh_init", "inflx_rh_advance_rk4", "inflx_rh_advance_rkf"}},
 };
 
 // Load the companion object `which` beside the core object, unless the handle has it: it must carry the core object's VERSION and
@@ -4263,6 +4268,80 @@ int inflx_inflation_end(inflx_model* m, const double* p, size_t P, size_t n_p, c
       if (states)
         for (int c = 0; c < 6; ++c) states[(c0 + l) * 6 + c] = hc[(size_t)(INFLX_HX_CARRY_Y + c) * n + l];
       if (t) t[c0 + l] = hc[INFLX_HX_CARRY_T * n + l];
+    }
+  }
+  return sf_verdict_lanes(m, nonfinite);
+}
+
+}  // extern "C"
+
+// ---- reheating: trajectories whose fields decay into radiation, to the point where the radiation dominates (inflx_reheating) ----
+extern "C" {
+
+int inflx_reheating(inflx_model* m, const double* p, size_t P, size_t n_p, const double* init, const double* gamma, const double* rho_r0, size_t B, double omega_r,
+                    size_t max_steps, int method, double max_err, double dt, double* states, double* t, double* h_start, int8_t* status) {
+  INFLX_SERIALISE(m);
+  auto own = [&]() -> int {
+    if (!(omega_r > 0.0 && omega_r < 1.0)) return fail(INFLX_ERR_ARG, "omega_r must be in (0, 1)");
+    if (B && !gamma) return fail(INFLX_ERR_ARG, "decay-rate array is NULL");
+    for (size_t l = 0; l < B; ++l) {
+      if (!(std::isfinite(gamma[l]) && gamma[l] >= 0.0)) return fail(INFLX_ERR_ARG, "decay rate %zu is not a finite number >= 0", l);
+      if (rho_r0 && !(std::isfinite(rho_r0[l]) && rho_r0[l] >= 0.0)) return fail(INFLX_ERR_ARG, "initial radiation density %zu is not a finite number >= 0", l);
+    }
+    return INFLX_OK;
+  };
+  int rc = check_integrator_args(m, "reheating requires", "trajectory", p, P, n_p, B, method, 0, 0, own, max_steps, max_err, dt, status);
+  if (rc) return rc;
+  if (B == 0) return INFLX_OK;
+  if (!init) return fail(INFLX_ERR_ARG, "initial-state array is NULL");
+  HIP_TRY(hipSetDevice(m->device));
+  if ((rc = need_companion(m, kObjReheating))) return rc;
+  hipStream_t s = m->stream;
+  // a lane returns nothing but its carry
+  const size_t nc_max = inflx_bg_lanes_per_pass(B, INFLX_RH_CARRY_PLANES * sizeof(double), INFLX_RH_THREADS);
+  DeviceBuffers dev;
+  double *d_p = nullptr, *d_init = nullptr, *d_gamma = nullptr, *d_rho = nullptr, *d_carry = nullptr;
+  uint32_t* d_running = nullptr;
+  if ((rc = dev.params(&d_p, p, P, n_p, s)) || (rc = dev.array(&d_init, nc_max * 4)) || (rc = dev.array(&d_gamma, nc_max)) || (rc = dev.array(&d_rho, nc_max)) ||
+      (rc = dev.array(&d_carry, nc_max * INFLX_RH_CARRY_PLANES)) || (rc = dev.array(&d_running, 1)))
+    return rc;
+  std::vector<double> host_carry(nc_max * INFLX_RH_CARRY_PLANES);
+  const CompanionSlot& rh = m->companion[kObjReheating];
+  hipFunction_t advance = rh.fn[kRhAdvance + (method == INFLX_EOM_RKF ? 1 : 0)];
+
+  bool nonfinite = false;  // a lane of the call stopped INFLX_EOM_NONFINITE
+  for (size_t c0 = 0; c0 < B; c0 += nc_max) {
+    const size_t n = std::min(nc_max, B - c0);
+    InflxRhArgs a;
+    memset(&a, 0, sizeof a);
+    a.p = d_p + (P == 1 ? 0 : c0 * n_p);
+    a.p_stride = P == 1 ? 0 : n_p;
+    a.init = d_init;
+    a.gamma = d_gamma;
+    a.rho_r0 = rho_r0 ? d_rho : nullptr;
+    a.carry = d_carry;
+    a.n = n;
+    a.max_err = max_err;
+    a.fixed_dt = dt;
+    a.omega_r = omega_r;
+    a.running = d_running;
+    void* params[] = {&a};
+    const unsigned grid = (unsigned)((n + INFLX_RH_THREADS - 1) / INFLX_RH_THREADS);
+    HIP_TRY(hipMemcpyAsync(d_init, init + c0 * 4, n * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_gamma, gamma + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    if (rho_r0) HIP_TRY(hipMemcpyAsync(d_rho, rho_r0 + c0, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipModuleLaunchKernel(rh.fn[kRhInit], grid, 1, 1, INFLX_RH_THREADS, 1, 1, 0, s, params, nullptr));
+    if ((rc = advance_until_done(advance, a, grid, INFLX_RH_THREADS, max_steps, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(host_carry.data(), d_carry, n * INFLX_RH_CARRY_PLANES * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const double* hc = host_carry.data();
+    for (size_t l = 0; l < n; ++l) {
+      status[c0 + l] = (int8_t)hc[INFLX_RH_CARRY_STATUS * n + l];
+      nonfinite |= status[c0 + l] == INFLX_EOM_NONFINITE;
+      if (states)
+        for (int c = 0; c < 7; ++c) states[(c0 + l) * 7 + c] = hc[(size_t)(INFLX_RH_CARRY_Y + c) * n + l];
+      if (t) t[c0 + l] = hc[INFLX_RH_CARRY_T * n + l];
+      if (h_start) h_start[c0 + l] = hc[INFLX_RH_CARRY_H0 * n + l];
     }
   }
   return sf_verdict_lanes(m, nonfinite);
